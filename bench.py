@@ -13,7 +13,16 @@ episode-done compaction -> in-kernel auto-reset), with synthetic actions already
 precision is "mixed" (fp32 derivative evaluations, fp64 state accumulate): the cheapest variant that meets the
 north-star 1e-4 parity gate over 1000 steps (tests/test_gpu_parity.py prints the measured drift of each variant).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with the driver's contract fields plus `parity` and `roofline`.  A plain run does only what
+that headline needs: set-up, W warm-up steps, ONE timed region of exactly K steps (`ms_per_step` = its wall time / K), the
+optional output dump, the line.  `--full` adds what is measured beside it: the short secondary workloads (`extras`), the CPU
+oracle baseline (`cpu_baseline`), the train leg of the N > 1 / `--single-rank-group` line, and repeats of a short timed
+region (median of R regions of K steps, `repeats`).
+
+`--dump-outputs DIR` writes what the timed path left for its caller after the last step of the (first) timed region --
+observations, rewards, termination flags and state for the env workloads -- as DIR/<name>.npy (float32 / float64, 64 MB at
+most: a fixed, seeded row sample of larger outputs, its indices in sample_rows.npy).  Inputs depend on the arguments only,
+so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -97,6 +106,11 @@ def parse():
     ap.add_argument("--ppo-steps", type=int, default=16, help="rollout length per PPO iteration (train workload)")
     ap.add_argument("--ppo-epochs", type=int, default=2)
     ap.add_argument("--ppo-minibatches", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (extras, CPU baseline, the train leg of the N > 1 line) and "
+                         "repeat a short timed region; a plain run times the K steps once and reports the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -198,6 +212,26 @@ class Workload:
             self.desc = (f"5-level cascade + 1 RK4 per 10 ms control step, {self.inner} control steps per launch, "
                          f"{n} aircraft/GPU, square mission (restarts)")
 
+    def outputs(self):
+        """What the timed path left for its caller after its last step: {name: (array, per_row)}, float32 / float64 on the
+        host.  per_row: the leading axis is the env / aircraft index (the one a size-capped dump samples)."""
+        def f(t, rows=True):
+            a = t.detach()
+            a = a.double() if a.dtype == torch.float64 else a.float()
+            return a.cpu().numpy(), rows
+        if self.kind == "train":
+            return {"params": f(torch.cat([p.detach().reshape(-1).float() for p in self.ppo.policy.parameters()]), False)}
+        if self.kind in ("physics", "cascade"):
+            return {"state": f(self.fleet.x.T)}
+        env = self.env
+        out = {"obs": f(env.obs), "rewards": f(env.rewards), "rewards_full": f(env.rewards_full), "terminated": f(env.terminated),
+               "truncated": f(env.truncated), "state": f(env.x.T)}
+        if self.kind == "rollout":
+            out["actions"] = f(env.actions_taken)
+            for name, t in zip(("pi_h", "pi_c", "vf_h", "vf_c"), self.ppo.states):
+                out[name] = f(t)
+        return out
+
     @torch.no_grad()
     def _rollout_step(self):
         """One policy + env step with every buffer updated in place (capture-safe)."""
@@ -292,11 +326,12 @@ def _grouped():
     return torch.distributed.is_available() and torch.distributed.is_initialized()
 
 
-def timed_region(wl, args, world, min_region_s=0.05, max_repeats=31):
+def timed_region(wl, args, world, min_region_s=0.05, max_repeats=31, after_first=None):
     """W warm-up steps, then EXACTLY K timed steps bracketed by barrier + synchronize; HIP events on the launch stream.
     When the K-step region is shorter than `min_region_s` (K = 20 launches of 68 us is 1.4 ms: two timer reads and a
     launch-queue hiccup are a tenth of it) the same K-step region is timed R times and the MEDIAN is reported
-    (`repeats` in the output); K itself never changes."""
+    (`repeats` in the output); K itself never changes.  min_region_s = 0: one region.  `after_first()` runs once, untimed,
+    right after the first region."""
     K, W = args.steps, args.warmup
     grp = world > 1 or (getattr(args, "single_rank_group", False) and _grouped())
     stream = torch.cuda.current_stream()
@@ -324,6 +359,8 @@ def timed_region(wl, args, world, min_region_s=0.05, max_repeats=31):
         return wall, dev_ms
 
     samples = [once()]
+    if after_first is not None:
+        after_first()
     repeats = 1
     if samples[0][0] < min_region_s:
         repeats = int(min(max_repeats, max(3, (0.25 / max(samples[0][0], 1e-6)))) // 2 * 2 + 1)      # odd
@@ -564,6 +601,31 @@ def cpu_baseline(args):
             "sample": f"oracle/flight_oracle.c (fp64, OpenMP), {n} envs x {reps} steps, {dt_all:.1f} s on {threads} threads"}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def write_outputs(arrays, path):
+    """{name: (array, per_row)} -> path/<name>.npy.  Past DUMP_BYTES in all, the per-row arrays keep a fixed row sample (seed
+    0, the same rows for every array, sorted; indices in sample_rows.npy) sized to fit."""
+    os.makedirs(path, exist_ok=True)
+    whole = sum(a.nbytes for a, rows in arrays.values() if not rows) + 4096 * (len(arrays) + 1)     # + .npy headers
+    per_row = {k: a for k, (a, rows) in arrays.items() if rows}
+    n_rows = {a.shape[0] for a in per_row.values()}
+    assert len(n_rows) <= 1, {k: a.shape for k, a in per_row.items()}
+    row_bytes = sum(a.nbytes // max(a.shape[0], 1) for a in per_row.values())
+    out = {k: a for k, (a, rows) in arrays.items() if not rows}
+    if per_row:
+        n = n_rows.pop()
+        if whole + n * row_bytes > DUMP_BYTES:
+            k = max(1, (DUMP_BYTES - whole) // (row_bytes + 8))          # + 8: the float64 index of a sampled row
+            idx = np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+            per_row = {name: a[idx] for name, a in per_row.items()}
+            out["sample_rows"] = idx.astype(np.float64)
+        out.update(per_row)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     # stdout carries exactly ONE line, the JSON: whatever libraries print there (gloo's "[Gloo] Rank ..." lines, RCCL
@@ -573,7 +635,12 @@ def main():
     os.dup2(2, 1)
     world, rank, _ = setup_dist(args)
     wl = Workload(args, rank)
-    wall, dev_ms, mode, rep = timed_region(wl, args, world)
+    dumped = {}
+
+    def snapshot():
+        if args.dump_outputs and rank == 0:
+            dumped.update(wl.outputs())
+    wall, dev_ms, mode, rep = timed_region(wl, args, world, min_region_s=0.05 if args.full else 0.0, after_first=snapshot)
     K = args.steps
     units = wl.units_per_step * K * world
     value = units / wall
@@ -582,7 +649,7 @@ def main():
     del wl
     torch.cuda.empty_cache()
     train = None
-    if (world > 1 or args.single_rank_group) and args.workload == "env" and not args.no_extras:
+    if args.full and (world > 1 or args.single_rank_group) and args.workload == "env" and not args.no_extras:
         # every rank runs it: it contains the collective.  A failure must not cost the headline line (a deterministic error
         # reaches every rank alike; a rank lost inside a collective ends the others at the process group's timeout)
         try:
@@ -591,6 +658,8 @@ def main():
             train = {"error": repr(ex)}
     if rank != 0:
         return
+    if args.dump_outputs:
+        write_outputs(dumped, args.dump_outputs)
     per_launch_s = dev_ms * 1e-3 / K
     alg_bytes = ALG_BYTES[args.workload] * units_per_step
     achieved = alg_bytes / per_launch_s / 1e9
@@ -633,9 +702,9 @@ def main():
         out["policy"] = pol
     if train is not None:
         out["train"] = train
-    if world == 1 and args.workload == "env" and not args.no_extras and not args.single_rank_group:
+    if args.full and world == 1 and args.workload == "env" and not args.no_extras and not args.single_rank_group:
         out["extras"] = extras(args)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args)
         except Exception as ex:  # the oracle is optional test infrastructure; never fail the measurement over it

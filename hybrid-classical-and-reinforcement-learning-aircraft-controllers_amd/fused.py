@@ -229,7 +229,7 @@ class _ZeroStateLayerFn(torch.autograd.Function):
             with torch.autocast("cuda", enabled=False):
                 w4 = w_ih.to(dt).contiguous()
                 w3 = torch.cat([w4[:H], w4[2 * H:]])                                          # rows of i, g, o (backward GEMMs)
-                b32 = (b_ih + b_hh).float().contiguous()
+                b32 = (b_ih + b_hh).to(dt).float().contiguous()                               # the bias in `dt`, as addmm below
             gates = torch.empty((M, 3 * H), dtype=dt, device=x.device)
             _lib.check(lib.fdyn_lstm_cell_mfma_train(x2.data_ptr(), x2.shape[1], None, 0, None, None, w4.data_ptr(), b32.data_ptr(),
                                                      h.data_ptr(), None, gates.data_ptr(), None, 0, None, M, H,
@@ -414,7 +414,7 @@ class _LSTMSequenceFn(torch.autograd.Function):
         if need and _mfma_train_ok(feats, kx, H, H):
             # every step of every cell is ONE MFMA kernel (GEMM + gate non-linearities + cell update + the activated gates for
             # the backward pass + the next step's recurrent input columns): no [B, 4H] pre-activations in HBM
-            wc, b32 = w.contiguous(), torch.stack([params[4 * g + 2] + params[4 * g + 3] for g in range(G)]).float().contiguous()
+            wc, b32 = w.contiguous(), b.float()              # the bias in `dt`, as the un-fused steps below add it
             h0c = h0.to(dt).contiguous()
             for t in range(T):
                 last = t == T - 1

@@ -69,3 +69,38 @@ def test_failed_children_propagate_a_nonzero_exit(monkeypatch, capsys):
     with pytest.raises(SystemExit) as ex:
         bench._self_launch_if_needed()
     assert ex.value.code == 3 and capsys.readouterr().out == ""
+
+
+def test_plain_run_leaves_the_secondary_measurements_to_full(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert a.steps == 20 and a.warmup == 5 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_fit_the_cap_with_one_fixed_row_sample(tmp_path):
+    import numpy as np
+    bench = _bench_module()
+    n = 1 << 21
+    rs = np.random.RandomState(1)
+    arrays = {"state": (rs.rand(n, 12), True), "obs": (rs.rand(n, 18).astype(np.float32), True),
+              "params": (np.arange(1000, dtype=np.float32), False)}
+    for d in ("a", "b"):
+        bench.write_outputs(arrays, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["obs.npy", "params.npy", "sample_rows.npy", "state.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and rows[-1] < n
+    idx = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "state.npy"), arrays["state"][0][idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "obs.npy"), arrays["obs"][0][idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "params.npy"), arrays["params"][0])
+    for f in files:                                     # same arguments, same files
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    small = {"obs": (np.ones((64, 18), np.float32), True)}
+    bench.write_outputs(small, str(tmp_path / "c"))
+    assert os.listdir(tmp_path / "c") == ["obs.npy"]                # under the cap: everything, no sample

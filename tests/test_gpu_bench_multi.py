@@ -9,7 +9,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--batch", "8192", "--ppo-steps", "4", "--ppo-epochs", "1",
+# --full: the train leg of the N > 1 line and the repeats of a short timed region are not part of a plain run
+COMMON = ["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--batch", "8192", "--ppo-steps", "4", "--ppo-epochs", "1",
           "--ppo-minibatches", "2"]
 
 
