@@ -15,6 +15,7 @@ _i, _i64, _u64, _d, _f = C.c_int, C.c_int64, C.c_uint64, C.c_double, C.c_float
 
 _SIXDOF = [_p, _p, _p, _p, _i, _i64, _d, _i, _p, _p]
 _CASCADE = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
+_HYBRID = [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i64, _d, _p]
 _ENV_RESET = [_p, _p, _p, _p, _p, _p, _p, _i, _u64, _p, _i64, _p]
 _ENV_STEP = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _u64, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p,
              _i, _i64, _p]
@@ -47,6 +48,7 @@ SIGNATURES = {
     "fdyn_agent_step_f64": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]),
     "fdyn_agent_step_mixed": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]),
     "fdyn_agent_step_f32": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]),
+    "fdyn_hybrid_step_f64": (_i, _HYBRID), "fdyn_hybrid_step_mixed": (_i, _HYBRID), "fdyn_hybrid_step_f32": (_i, _HYBRID),
     "fdyn_colsum_ws_floats": (_i64, [_i64, _i, _i64, _i]),
     "fdyn_colsum": (_i, [_p, _i, _i64, _i, _i64, _i, _p, _p, _p]),
     "fdyn_ppo_loss": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _f, _i64, _p, _p, _p, _p, _p]),

@@ -243,12 +243,36 @@ class _SingleAgent:
         row = command_row(command)
         f = self._fleet
         f.x.copy_(torch.as_tensor(state.to_vector(), device=f.device).to(f.dtype).reshape(L.FD_NX, 1))
+        if getattr(self, "rate_agent", None) is not None:
+            return self._compute_with_rate_agent(row, state, self._default_dt() if dt is None else dt)
         s = f.compute_action(self.LEVEL, row, self._default_dt() if dt is None else dt)[:, 0].to(torch.float64).cpu().numpy()
         return ControlSurfaces(elevator=float(s[L.FD_U_ELEVATOR]), aileron=float(s[L.FD_U_AILERON]),
                                rudder=float(s[L.FD_U_RUDDER]), throttle=float(s[L.FD_U_THROTTLE]))
 
+    def _compute_with_rate_agent(self, row, state: AircraftState, dt: float) -> ControlSurfaces:
+        """attitude_agent.py:152 with `self.rate_agent` replaced: the outer loops of this level run on the device
+        (fdyn_hybrid_step_* without actions: no physics, rate PID untouched) and hand ControlCommand(RATE, p, q, r, throttle)
+        to the inner agent."""
+        from .hybrid import hybrid_step
+        f = self._fleet
+        if f.cfg_per_lane:
+            raise ValueError("per-aircraft gain tables are not supported with a replaced rate_agent")
+        if getattr(self, "_hyb", None) is None:
+            z = lambda *shape, dt_=torch.float32: torch.zeros(shape, dtype=dt_, device=f.device)   # noqa: E731
+            self._hyb = {"prev": z(1, L.FD_ACT_DIM), "obs": z(1, L.FD_OBS_DIM), "rate": z(4, 1), "surf": z(L.FD_NU, 1, dt_=f.dtype)}
+        h = self._hyb
+        cmd = f._cmd(row)
+        hybrid_step(getattr(f.lib, f"fdyn_hybrid_step_{f.precision}"), self.LEVEL, f.x, f.pid_state, None, f.type_index, f.params,
+                    f.n_types, f.pid_cfg, f.consts, cmd, None, 0, None, None, L.FD_HYBRID_THROTTLE_POLICY, h["prev"], h["obs"],
+                    h["rate"], h["surf"], None, 1, dt)
+        p, q, r, thr = (float(v) for v in h["rate"][:, 0].cpu())
+        inner = ControlCommand(mode=ControlMode.RATE, roll_rate=p, pitch_rate=q, yaw_rate=r, throttle=thr)
+        return self.rate_agent.compute_action(inner, state, dt)
+
     def reset(self):
         self._fleet.reset_agents()
+        if getattr(self, "rate_agent", None) is not None:
+            self.rate_agent.reset()
 
     def __repr__(self) -> str:
         return f"{type(self).__name__}(level={self.MODE.name})"
@@ -271,6 +295,7 @@ class AttitudeAgent(_SingleAgent):
 
     def __init__(self, config: ControllerConfig, precision: str = "f64"):
         super().__init__(config, precision=precision)
+        self.rate_agent = None              # attitude_agent.py:67; assign a LearnedRateAgent for the hybrid composition
 
 
 class HSAAgent(_SingleAgent):
@@ -279,6 +304,7 @@ class HSAAgent(_SingleAgent):
 
     def __init__(self, config: ControllerConfig, flight_config: Optional[FlightControlConfig] = None, precision: str = "f64"):
         super().__init__(config, flight_config, precision=precision)
+        self.rate_agent = None              # the inner loop under the attitude stage (None: the PID RateAgent)
 
 
 class WaypointAgent(_SingleAgent):
@@ -288,6 +314,7 @@ class WaypointAgent(_SingleAgent):
     def __init__(self, config: ControllerConfig, guidance_type: str = "LOS", flight_config: Optional[FlightControlConfig] = None,
                  precision: str = "f64"):
         super().__init__(config, flight_config, guidance_type, precision)
+        self.rate_agent = None              # the inner loop under the attitude stage (None: the PID RateAgent)
         self.guidance_type = guidance_type
         g = flight_config.guidance if flight_config is not None else GuidanceConfig()
         self.acceptance_radius = g.acceptance_radius

@@ -1053,10 +1053,22 @@ FD_DEV Surfaces<G> rate_agent(const PidCfg* cfg, PidState* st, const G* C, G p_c
     return s;
 }
 
+// The stage below the attitude loop (attitude_agent.py:67,152 holds it as `self.rate_agent` and calls its compute_action).
+// Default: the PID rate agent above.  The hybrid kernel passes a stage that hands the rate command to a learned policy on
+// some lanes instead; the outer agents take it as a template parameter so that every other kernel keeps the PID inline.
+struct PidRateStage {
+    template <typename G>
+    FD_DEV Surfaces<G> operator()(const PidCfg* cfg, PidState* st, const G* C, G p_cmd, G q_cmd, G r_cmd, G throttle,
+                                  const G (&x)[FD_NX], G dt) const
+    {
+        return rate_agent<G>(cfg, st, C, p_cmd, q_cmd, r_cmd, throttle, x, dt);
+    }
+};
+
 // controllers/attitude_agent.py:116-152
-template <typename G>
+template <typename G, typename Inner = PidRateStage>
 FD_DEV Surfaces<G> attitude_agent(const PidCfg* cfg, PidState* st, const G* C, G roll_cmd, G pitch_cmd, G yaw_cmd,
-                                  bool has_yaw, G throttle, const G (&x)[FD_NX], G dt)
+                                  bool has_yaw, G throttle, const G (&x)[FD_NX], G dt, Inner&& inner = Inner())
 {
     roll_cmd = clipv(roll_cmd, -C[FD_C_MAX_ROLL], C[FD_C_MAX_ROLL]);
     pitch_cmd = clipv(pitch_cmd, -C[FD_C_MAX_PITCH], C[FD_C_MAX_PITCH]);
@@ -1069,13 +1081,13 @@ FD_DEV Surfaces<G> attitude_agent(const PidCfg* cfg, PidState* st, const G* C, G
     const G p_cmd = clipv(G(o_r), -C[FD_C_MAX_ROLL_RATE], C[FD_C_MAX_ROLL_RATE]);
     const G q_cmd = clipv(G(o_p), -C[FD_C_MAX_PITCH_RATE], C[FD_C_MAX_PITCH_RATE]);
     const G r_cmd = clipv(G(o_y), -C[FD_C_MAX_YAW_RATE], C[FD_C_MAX_YAW_RATE]);
-    return rate_agent<G>(cfg, st, C, p_cmd, q_cmd, r_cmd, throttle, x, dt);
+    return inner(cfg, st, C, p_cmd, q_cmd, r_cmd, throttle, x, dt);
 }
 
 // controllers/hsa_agent.py:149-229
-template <typename G>
+template <typename G, typename Inner = PidRateStage>
 FD_DEV Surfaces<G> hsa_agent(const PidCfg* cfg, PidState* st, const G* C, G heading_cmd, G speed_cmd, G altitude_cmd,
-                             const G (&x)[FD_NX], const Derived<G>& d, G dt)
+                             const G (&x)[FD_NX], const Derived<G>& d, G dt, Inner&& inner = Inner())
 {
     const G heading_error = wrap_angle<G>(heading_cmd - d.heading);
     const G virtual_setpoint = d.heading + heading_error;
@@ -1101,7 +1113,7 @@ FD_DEV Surfaces<G> hsa_agent(const PidCfg* cfg, PidState* st, const G* C, G head
         pitch_angle += C[FD_C_LOAD_FACTOR_GAIN] * (load_factor - G(1));
     }
     pitch_angle = clipv(pitch_angle, -C[FD_C_MAX_PITCH_CMD_RAD], C[FD_C_MAX_PITCH_CMD_RAD]);
-    return attitude_agent<G>(cfg, st, C, roll_angle, pitch_angle, x[8], true, throttle, x, dt);
+    return attitude_agent<G>(cfg, st, C, roll_angle, pitch_angle, x[8], true, throttle, x, dt, static_cast<Inner&&>(inner));
 }
 
 template <typename G> FD_DEV G wrap_pi(G a)
@@ -1116,9 +1128,9 @@ template <typename G> FD_DEV G wrap_pi(G a)
 }
 
 // controllers/waypoint_agent.py:107-242 ; wp = {north, east, altitude, speed}
-template <typename G>
+template <typename G, typename Inner = PidRateStage>
 FD_DEV Surfaces<G> waypoint_agent(const PidCfg* cfg, PidState* st, const G* C, const G* wp, const G (&x)[FD_NX],
-                                  const Derived<G>& d, G dt)
+                                  const Derived<G>& d, G dt, Inner&& inner = Inner())
 {
     const G e0 = wp[FD_WP_NORTH] - x[0], e1 = wp[FD_WP_EAST] - x[1];
     const G hd = M<G>::sqrt(e0 * e0 + e1 * e1);
@@ -1162,7 +1174,7 @@ FD_DEV Surfaces<G> waypoint_agent(const PidCfg* cfg, PidState* st, const G* C, c
         const G reduction = C[FD_C_MAX_SPEED_REDUCTION] * (G(1) - hd / td);
         speed_cmd = pymax(speed_cmd * (G(1) - reduction), C[FD_C_MIN_SPEED]);
     }
-    return hsa_agent<G>(cfg, st, C, heading_cmd, speed_cmd, wp[FD_WP_ALTITUDE], x, d, dt);
+    return hsa_agent<G>(cfg, st, C, heading_cmd, speed_cmd, wp[FD_WP_ALTITUDE], x, d, dt, static_cast<Inner&&>(inner));
 }
 
 // controllers/mission_planner.py:128-184 : 3-D acceptance test on the current waypoint

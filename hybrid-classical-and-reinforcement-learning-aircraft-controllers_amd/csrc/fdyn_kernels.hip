@@ -401,6 +401,206 @@ agent_step_kernel(int level, S* __restrict__ xs, float* __restrict__ pid_state /
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Hybrid cascade: PID outer loops over a learned (or PID) rate loop, one control step per launch
+//   (controllers/attitude_agent.py:67,152 with `rate_agent = LearnedRateAgent(...)`, learned_rate_agent.py:128-198;
+//    gui/simulation_worker_learned.py:51-118 switches the inner agent per aircraft)
+// The policy runs between launches (its own kernels), so a launch is
+//   1. apply: the surfaces of this control step -- the clipped policy action on learned lanes, the surfaces the rate PID
+//      produced in the previous launch on PID lanes -- then one RK4 of dt;
+//   2. the mission update and the outer agents on the new state, ending in a rate command + throttle;
+//   3. PID lanes: the rate PID (its surfaces -> surf_out for the next launch); every lane: the policy observation.
+// With actions == NULL only 2 and 3 run (x untouched): the priming call.
+// ---------------------------------------------------------------------------------------------------------
+// The stage under the attitude loop on a hybrid lane: records the rate command and throttle it is handed; runs the rate PID
+// only where the lane is PID-controlled (its state advances only there).
+template <typename G> struct HybridRateStage {
+    bool pid;
+    G p, q, r, thr;
+    FD_DEV Surfaces<G> operator()(const PidCfg* cfg, PidState* st, const G* C, G p_cmd, G q_cmd, G r_cmd, G throttle,
+                                  const G (&x)[FD_NX], G dt)
+    {
+        p = p_cmd; q = q_cmd; r = r_cmd; thr = clipv(throttle, G(0), G(1));      // rate_agent.py:122 / action bounds
+        if (pid) return rate_agent<G>(cfg, st, C, p_cmd, q_cmd, r_cmd, throttle, x, dt);
+        return Surfaces<G>{ G(0), G(0), G(0), thr };
+    }
+};
+
+// (FD_BLOCK, 1) as the cascade: the same nine PID configurations / states, constants and integrator state in registers
+template <typename S, typename T>
+__global__ void __launch_bounds__(FD_BLOCK, 1)
+hybrid_step_kernel(int level, S* __restrict__ xs, float* __restrict__ pid_state /*[9*3][n]*/, int32_t* __restrict__ wp_idx,
+                   const uint8_t* __restrict__ type, const double* __restrict__ params, int n_types,
+                   const float* __restrict__ pid_cfg, const double* __restrict__ consts, const S* __restrict__ cmd /*[4][n]*/,
+                   const double* __restrict__ wps, int n_wp, const float* __restrict__ actions /*[n][4] or null*/,
+                   const uint8_t* __restrict__ learned /*[n] or null = all*/, int throttle_src,
+                   float* __restrict__ prev_action /*[n][4]*/, float* __restrict__ obs_out /*[n][18]*/,
+                   float* __restrict__ rate_cmd_out /*[4][n] or null*/, S* __restrict__ surf_out /*[4][n]*/,
+                   int32_t* __restrict__ reached_total, int64_t n, S dt)
+{
+    using G = typename GlueOf<S, T>::type;
+    constexpr bool FAST = sizeof(T) == 4;
+    __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
+    __shared__ float s_pid_cfg[FD_NPID * FD_NPC];
+    __shared__ G s_consts[FD_NC_STAGED];
+    __shared__ G s_wps[FD_MAX_WAYPOINTS * FD_NWP];
+    const LaneMap lm = lane_map(n);
+    const int64_t i = lm.i;
+    const bool mission = wps != nullptr;
+    PidState st[FD_NPID];
+    S x[FD_NX];
+    int32_t idx = 0;
+    int ty = 0;
+    bool is_pid = false;
+    if (lm.on) {                                             // per-aircraft loads in flight during the staging below
+#pragma unroll
+        for (int k = 0; k < FD_NPID; ++k)
+            st[k] = PidState{ pid_state[(k * FD_NPS + FD_PS_INTEGRAL) * n + i], pid_state[(k * FD_NPS + FD_PS_ERR_PREV) * n + i],
+                              pid_state[(k * FD_NPS + FD_PS_DFILT) * n + i] };
+#pragma unroll
+        for (int k = 0; k < FD_NX; ++k) x[k] = xs[k * n + i];
+        if (mission) idx = wp_idx[i];
+        ty = lane_type(type, i, n_types);
+        is_pid = learned ? learned[i] == 0 : false;
+    }
+    stage_params<FAST>(s_params, params, n_types);
+    stage(s_pid_cfg, pid_cfg, FD_NPID * FD_NPC);
+    stage_cascade_consts<G>(s_consts, consts);
+    for (int k = threadIdx.x; k < n_wp * FD_NWP; k += blockDim.x) s_wps[k] = G(wps[k]);
+    __syncthreads();
+    if (!lm.on) return;
+
+    const double* blk = s_params + ty * FD_NP_STAGED;
+    Params<T> P; P.load(blk);
+    Limits<S> Lm; Lm.load(blk);
+    PidCfg cfg[FD_NPID];
+#pragma unroll
+    for (int k = 0; k < FD_NPID; ++k) cfg[k] = load_pid_cfg(s_pid_cfg, k);
+    G Cr[FD_NC_STAGED];
+#pragma unroll
+    for (int k = 0; k < FD_NC_STAGED; ++k) Cr[k] = s_consts[k];
+    const bool restart = int(Cr[FD_C_ON_COMPLETE]) == 1;
+    // a mission the previous launch found complete (freeze): no physics, as the cascade's `break`
+    bool frozen = mission && idx >= n_wp && !restart;
+    float pa[FD_ACT_DIM];
+#pragma unroll
+    for (int k = 0; k < FD_ACT_DIM; ++k) pa[k] = prev_action[i * FD_ACT_DIM + k];
+    const G gdt = G(dt);
+
+    // ---- 1. apply ------------------------------------------------------------------------------------------------
+    Surfaces<G> applied{ G(0), G(0), G(0), G(0) };
+    if (actions) {
+        const G thr_outer = G(surf_out[FD_U_THROTTLE * n + i]);
+        if (!is_pid) {                                       // policy action [ail, elev, rud, thr], clipped to the action space
+#pragma unroll
+            for (int k = 0; k < FD_ACT_DIM; ++k) {
+                const float a = actions[i * FD_ACT_DIM + k];
+                pa[k] = clipv(a, k == 3 ? 0.0f : -1.0f, 1.0f);
+                prev_action[i * FD_ACT_DIM + k] = pa[k];
+            }
+            applied = Surfaces<G>{ G(pa[1]), G(pa[0]), G(pa[2]),
+                                   throttle_src == FD_HYBRID_THROTTLE_POLICY ? G(pa[3]) : thr_outer };
+        } else {
+            applied = Surfaces<G>{ G(surf_out[FD_U_ELEVATOR * n + i]), G(surf_out[FD_U_AILERON * n + i]),
+                                   G(surf_out[FD_U_RUDDER * n + i]), thr_outer };
+        }
+        if (!frozen) {
+            Controls<T> C;
+            C.set(P, applied.elevator, applied.aileron, applied.rudder, applied.throttle);
+            if constexpr (FAST) {
+                FastRK f;
+                f.init(x);
+                rk4_fast_step<S, false>(P, Lm, C, x, f, float(S(0.5) * dt), float(dt), float(dt / S(6)));
+            } else {
+                rk4_substeps<S, T>(P, Lm, C, x, dt, 1);
+            }
+        }
+    }
+
+    // ---- 2. mission update + outer loops on the new state ---------------------------------------------------------
+    // the fp32-evaluation glue reads a FastRK built afresh from the stored state -- exactly what a one-step cascade launch sees
+    // (a K-step launch carries the incrementally rotated trigonometry across steps instead)
+    HybridRateStage<G> inner;
+    inner.pid = is_pid;
+    inner.p = inner.q = inner.r = inner.thr = G(0);
+    Surfaces<G> surf{ G(0), G(0), G(0), G(0) };
+    int32_t reached = 0;
+    auto outer = [&](const G (&xg)[FD_NX], auto&& derive) {
+        if (mission) {
+            if (idx < n_wp && waypoint_reached<G>(Cr, s_wps + idx * FD_NWP, xg)) { idx += 1; reached += 1; }   // mission.update
+            if (idx >= n_wp) { if (restart) idx = 0; else frozen = true; }
+            if (!frozen) surf = waypoint_agent<G>(cfg, st, Cr, s_wps + idx * FD_NWP, xg, derive(), gdt, inner);
+            return;
+        }
+        const G c0 = G(cmd[i]), c1 = G(cmd[n + i]), c2 = G(cmd[2 * n + i]), c3 = G(cmd[3 * n + i]);
+        if (level == FD_LEVEL_ATTITUDE) {
+            const bool has_yaw = c2 == c2;
+            surf = attitude_agent<G>(cfg, st, Cr, c0, c1, has_yaw ? c2 : G(0), has_yaw, c3, xg, gdt, inner);
+        } else if (level == FD_LEVEL_HSA) {
+            surf = hsa_agent<G>(cfg, st, Cr, c0, c1, c2, xg, derive(), gdt, inner);
+        } else {
+            const G wp[FD_NWP] = { c0, c1, c2, c3 };
+            surf = waypoint_agent<G>(cfg, st, Cr, wp, xg, derive(), gdt, inner);
+        }
+    };
+    if constexpr (FAST) {
+        FastRK f;
+        f.init(x);
+        outer(f.x0, [&]() { return derived_fast(f); });
+    } else {
+        outer(x, [&]() { return derived<S>(x); });
+    }
+
+    // ---- 3. inner loop outputs ---------------------------------------------------------------------------------------
+#pragma unroll
+    for (int k = 0; k < FD_NX; ++k) if (actions) xs[k * n + i] = x[k];
+#pragma unroll
+    for (int k = 0; k < FD_NPID; ++k) {
+        pid_state[(k * FD_NPS + FD_PS_INTEGRAL) * n + i] = st[k].integral;
+        pid_state[(k * FD_NPS + FD_PS_ERR_PREV) * n + i] = st[k].err_prev;
+        pid_state[(k * FD_NPS + FD_PS_DFILT) * n + i] = st[k].dfilt;
+    }
+    if (mission) {
+        wp_idx[i] = idx;
+        if (reached_total) reached_total[i] += reached;
+    }
+    // PID lanes: the surfaces the next launch applies (zero when frozen, as the cascade's surf_out).  Learned lanes: the
+    // outer-loop throttle (read back by the next launch under FD_HYBRID_THROTTLE_OUTER) and the surfaces applied here.
+    if (is_pid) {
+        surf_out[FD_U_ELEVATOR * n + i] = S(surf.elevator); surf_out[FD_U_AILERON * n + i] = S(surf.aileron);
+        surf_out[FD_U_RUDDER * n + i] = S(surf.rudder);
+    } else if (actions) {
+        surf_out[FD_U_ELEVATOR * n + i] = S(applied.elevator); surf_out[FD_U_AILERON * n + i] = S(applied.aileron);
+        surf_out[FD_U_RUDDER * n + i] = S(applied.rudder);
+    }
+    surf_out[FD_U_THROTTLE * n + i] = S(surf.throttle);
+    // the rate command handed to the inner loop, narrowed to fp32: what rate_cmd_out reports and what the observation is built
+    // from, so that a host composition fed rate_cmd_out assembles the same observation (learned_rate_agent.py:152-178)
+    const float rc[4] = { float(inner.p), float(inner.q), float(inner.r), float(inner.thr) };
+    if (rate_cmd_out) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rate_cmd_out[k * n + i] = rc[k];
+    }
+    {
+#pragma clang fp contract(off)
+        // clip and differences in the state's precision, then narrowed (rate_env.py:374-408)
+        float* o = obs_out + i * FD_OBS_DIM;
+        const double mr[3] = { consts[FD_C_MAX_ROLL_RATE], consts[FD_C_MAX_PITCH_RATE], consts[FD_C_MAX_YAW_RATE] };
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const S c = clipv(S(rc[k]), -S(mr[k]), S(mr[k]));
+            o[k] = float(x[9 + k]);
+            o[3 + k] = float(c);
+            o[6 + k] = float(c - x[9 + k]);
+        }
+        o[9] = float(M<S>::sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]));
+        o[10] = float(-x[2]);
+        o[11] = float(x[6]); o[12] = float(x[7]); o[13] = float(x[8]);
+#pragma unroll
+        for (int k = 0; k < FD_ACT_DIM; ++k) o[14 + k] = pa[k];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // K3+K4: RateControlEnv.step for a whole vec-env, with done compaction and in-kernel auto-reset
 // ---------------------------------------------------------------------------------------------------------
 template <typename G> struct EnvConsts {
@@ -1056,6 +1256,31 @@ int fdyn_pid_compute_batch(const float* cfg, int cfg_per_lane, float* state, con
 FD_DEFINE_AGENT(fdyn_agent_step_f64, double, double)
 FD_DEFINE_AGENT(fdyn_agent_step_mixed, double, float)
 FD_DEFINE_AGENT(fdyn_agent_step_f32, float, float)
+
+#define FD_DEFINE_HYBRID(NAME, S, T)                                                                         \
+    int NAME(int level, S* x, float* pid_state, int32_t* wp_idx, const uint8_t* type, const double* params, int n_types, \
+             const float* pid_cfg, const double* consts, const S* cmd, const double* wps, int n_wp, const float* actions, \
+             const uint8_t* learned, int throttle_src, float* prev_action, float* obs_out, float* rate_cmd_out,  \
+             S* surf_out, int32_t* reached_total, int64_t n, double dt, void* stream)                         \
+    {                                                                                                        \
+        FD_CHECK_COMMON(n, n_types)                                                                          \
+        if (level != FD_LEVEL_WAYPOINT && level != FD_LEVEL_HSA && level != FD_LEVEL_ATTITUDE) return FDYN_ERR_BAD_SIZE; \
+        if (throttle_src != FD_HYBRID_THROTTLE_POLICY && throttle_src != FD_HYBRID_THROTTLE_OUTER) return FDYN_ERR_BAD_SIZE; \
+        if (wps && (level != FD_LEVEL_WAYPOINT || n_wp < 1 || n_wp > FD_MAX_WAYPOINTS || cmd)) return FDYN_ERR_BAD_SIZE; \
+        if (!wps && n_wp != 0) return FDYN_ERR_BAD_SIZE;                                                     \
+        if (!x || !pid_state || !params || !pid_cfg || !consts || !prev_action || !obs_out || !surf_out)     \
+            return FDYN_ERR_NULL;                                                                            \
+        if (wps ? !wp_idx : !cmd) return FDYN_ERR_NULL;                                                      \
+        if (!(dt > 1e-6) || dt > 1.0) return FDYN_ERR_BAD_DT;                                                \
+        hipLaunchKernelGGL((hybrid_step_kernel<S, T>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
+                           level, x, pid_state, wp_idx, type, params, n_types, pid_cfg, consts, cmd, wps, n_wp, \
+                           actions, learned, throttle_src, prev_action, obs_out, rate_cmd_out, surf_out,     \
+                           reached_total, n, S(dt));                                                         \
+        return launch_status();                                                                              \
+    }
+FD_DEFINE_HYBRID(fdyn_hybrid_step_f64, double, double)
+FD_DEFINE_HYBRID(fdyn_hybrid_step_mixed, double, float)
+FD_DEFINE_HYBRID(fdyn_hybrid_step_f32, float, float)
 
 FD_DEFINE_CASCADE(fdyn_cascade_step_f64, double, double)
 FD_DEFINE_CASCADE(fdyn_cascade_step_mixed, double, float)

@@ -23,6 +23,9 @@
  *                          controllers/{mission_planner.py:128-184, waypoint_agent.py:81-242, hsa_agent.py:119-231,
  *                          attitude_agent.py:86-154, rate_agent.py:65-124}
  *   fdyn_agent_step_*      {Rate,Attitude,HSA,Waypoint}Agent.compute_action (+ set_controls + step): one level commanded directly
+ *   fdyn_hybrid_step_*     AttitudeAgent / HSAAgent / WaypointAgent with `rate_agent` = LearnedRateAgent or the PID RateAgent,
+ *                          chosen per aircraft and switched live   controllers/attitude_agent.py:67,152,
+ *                          controllers/learned_rate_agent.py:128-198, gui/simulation_worker_learned.py:51-118
  *   fdyn_rate_env_reset_*  RateControlEnv.reset              learned_controllers/envs/rate_env.py:151-210
  *   fdyn_rate_env_step_*   RateControlEnv.step (+ the vec-env's auto-reset, + optionally the PID demonstrator of
  *                          learned_controllers/utils/pid_demonstrations.py:47-77)
@@ -121,6 +124,35 @@ int fdyn_agent_step_mixed(int level, double* x, float* pid_state, const uint8_t*
 int fdyn_agent_step_f32(int level, float* x, float* pid_state, const uint8_t* type, const double* params, int n_types,
                         const float* pid_cfg, int cfg_per_lane, const double* consts, const float* cmd, int64_t n, double dt,
                         int n_steps, float* surf_out, void* stream);
+
+/* ---- hybrid cascade: PID outer loops over a learned or PID rate loop, per aircraft -------------------------------------------
+ * One control step per launch; the policy runs between launches on obs_out.
+ *   1. apply (only if actions != NULL): learned lanes (learned[i] != 0, or learned == NULL) take actions [n][4] = [ail, elev, rud,
+ *      thr], clipped to -1..1 (throttle 0..1) and stored to prev_action [n][4]; PID lanes take the surfaces the rate PID wrote
+ *      to surf_out in the previous launch.  The throttle of a learned lane is the policy's (FD_HYBRID_THROTTLE_POLICY) or the
+ *      outer loop's (FD_HYBRID_THROTTLE_OUTER, read back from surf_out).  Then one RK4 of dt (none for a frozen mission).
+ *   2. the mission update (wps != NULL: level must be FD_LEVEL_WAYPOINT, 1 <= n_wp <= 16, cmd NULL; wp_idx / reached_total as
+ *      fdyn_cascade_step_*) or the command cmd [4][n] (as fdyn_agent_step_* at `level`), then the waypoint / HSA / attitude agent
+ *      on the new state, ending in a rate command p, q, r + throttle.
+ *   3. PID lanes run the rate PID (its state rows advance only there) -> surf_out [4][n] for the next launch; learned lanes
+ *      get the outer throttle in surf_out's throttle row and the surfaces applied in step 1 in the others.  Every lane: the
+ *      policy observation obs_out [n][18] fp32 (rate_env.py:374-408 layout; command clipped to the max rates, differences
+ *      and airspeed in the state's precision) and, if not NULL, rate_cmd_out [4][n] fp32 = p, q, r, throttle.
+ * actions == NULL runs 2 and 3 only (x untouched): the priming call, and the single-aircraft agents' compute_action.
+ * The fp32-evaluation variants rebuild their integrator trigonometry from the stored state every launch, so K launches
+ * equal K one-step cascade launches bit for bit on PID lanes.                                                                 */
+int fdyn_hybrid_step_f64(int level, double* x, float* pid_state, int32_t* wp_idx, const uint8_t* type, const double* params,
+                         int n_types, const float* pid_cfg, const double* consts, const double* cmd, const double* wps, int n_wp,
+                         const float* actions, const uint8_t* learned, int throttle_src, float* prev_action, float* obs_out,
+                         float* rate_cmd_out, double* surf_out, int32_t* reached_total, int64_t n, double dt, void* stream);
+int fdyn_hybrid_step_mixed(int level, double* x, float* pid_state, int32_t* wp_idx, const uint8_t* type, const double* params,
+                           int n_types, const float* pid_cfg, const double* consts, const double* cmd, const double* wps, int n_wp,
+                           const float* actions, const uint8_t* learned, int throttle_src, float* prev_action, float* obs_out,
+                           float* rate_cmd_out, double* surf_out, int32_t* reached_total, int64_t n, double dt, void* stream);
+int fdyn_hybrid_step_f32(int level, float* x, float* pid_state, int32_t* wp_idx, const uint8_t* type, const double* params,
+                         int n_types, const float* pid_cfg, const double* consts, const float* cmd, const double* wps, int n_wp,
+                         const float* actions, const uint8_t* learned, int throttle_src, float* prev_action, float* obs_out,
+                         float* rate_cmd_out, float* surf_out, int32_t* reached_total, int64_t n, double dt, void* stream);
 
 /* ---- rate-control env ------------------------------------------------------------------------------------------
  * x [FD_NX][n] ; e [FD_NE][n] (FD_E_*; fp64 in the f64 variant, fp32 in mixed and f32 -- there FD_E_SETTLE_TIMER counts settled

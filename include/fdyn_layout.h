@@ -87,6 +87,9 @@ enum { FD_GUIDANCE_LOS = 0, FD_GUIDANCE_PP = 1, FD_GUIDANCE_DEFAULT = 2 };
 /* control levels, numbered as the reference's ControlMode (controllers/types.py:13-24): the level a command enters at */
 enum { FD_LEVEL_WAYPOINT = 1, FD_LEVEL_HSA = 2, FD_LEVEL_ATTITUDE = 3, FD_LEVEL_RATE = 4 };
 enum { FD_WP_NORTH = 0, FD_WP_EAST, FD_WP_ALTITUDE, FD_WP_SPEED, FD_NWP = 4 };  /* waypoint row */
+/* hybrid cascade (fdyn_hybrid_step_*): where a learned lane's throttle comes from -- the policy's fourth action word (what the
+ * reference does with a LearnedRateAgent under an AttitudeAgent) or the outer loop's throttle (what a mission usually wants) */
+enum { FD_HYBRID_THROTTLE_POLICY = 0, FD_HYBRID_THROTTLE_OUTER = 1 };
 #define FD_MAX_WAYPOINTS 16
 
 /* ---- rate-control env, learned_controllers/envs/rate_env.py ------------------------------------------ */
