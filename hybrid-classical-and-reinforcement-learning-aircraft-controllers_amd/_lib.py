@@ -19,6 +19,8 @@ _HYBRID = [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _
 _ENV_RESET = [_p, _p, _p, _p, _p, _p, _p, _i, _u64, _p, _i64, _p]
 _ENV_STEP = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _u64, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p,
              _i, _i64, _p]
+_ENV_RESET_DR = _ENV_RESET[:-1] + [_p, _p, _p]               # + dr, dr_consts before the stream
+_ENV_STEP_DR = _ENV_STEP[:-1] + [_p, _p, _p]
 
 SIGNATURES = {
     "fdyn_abi_version": (_i, []),
@@ -33,6 +35,10 @@ SIGNATURES = {
     "fdyn_rate_env_reset_f32": (_i, _ENV_RESET),
     "fdyn_rate_env_step_f64": (_i, _ENV_STEP), "fdyn_rate_env_step_mixed": (_i, _ENV_STEP),
     "fdyn_rate_env_step_f32": (_i, _ENV_STEP),
+    "fdyn_rate_env_reset_dr_f64": (_i, _ENV_RESET_DR), "fdyn_rate_env_reset_dr_mixed": (_i, _ENV_RESET_DR),
+    "fdyn_rate_env_reset_dr_f32": (_i, _ENV_RESET_DR),
+    "fdyn_rate_env_step_dr_f64": (_i, _ENV_STEP_DR), "fdyn_rate_env_step_dr_mixed": (_i, _ENV_STEP_DR),
+    "fdyn_rate_env_step_dr_f32": (_i, _ENV_STEP_DR),
     "fdyn_lstm_cell_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
     "fdyn_lstm_cell_bwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
     "fdyn_lstm_seq_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i, _p]),

@@ -415,19 +415,64 @@ template <typename T> struct Controls {
     }
 };
 
+// ----- domain randomisation (the rate env's _dr entry points) ------------------------------------------------------
+// Air-mass velocity in NED (steady wind + gust, constant over one env step).  The aerodynamics see the air-relative body
+// velocity v - R^T W; kinematics and the -omega x v terms keep the stored ground-relative one.  Kernels built without
+// randomisation never instantiate the WIND forms below.
+template <typename T> struct Wind { T n, e, d; };
+// R^T W for the Euler angles given by (sin, cos) pairs: yaw, then pitch, then roll as three plane rotations.  Contraction off:
+// with W = 0 every product is +-0 and so is the result, which the neutral-range bit-identity argument relies on.
+template <typename T>
+FD_DEV void body_wind(T sphi, T cphi, T sth, T cth, T spsi, T cpsi, const Wind<T>& w, T& bu, T& bv, T& bw)
+{
+#pragma clang fp contract(off)
+    const T a = cpsi * w.n + spsi * w.e, b = cpsi * w.e - spsi * w.n;
+    bu = cth * a - sth * w.d;
+    const T c = sth * a + cth * w.d;
+    bv = cphi * b + sphi * c;
+    bw = cphi * c - sphi * b;
+}
+// per-env multipliers on the lane's copy of its type's block: mass, inertias and air density, and every derived word or packed
+// pair that holds one of them.  Multiplying by 1 and recomputing differences / reciprocals of unchanged values is exact.
+template <typename T>
+FD_DEV void scale_params(Params<T>& P, double ms, double ixs, double iys, double izs, double rs)
+{
+#pragma clang fp contract(off)
+    P.mass = P.mass * T(ms);
+    P.ixx = P.ixx * T(ixs); P.iyy = P.iyy * T(iys); P.izz = P.izz * T(izs);
+    if constexpr (sizeof(T) == 8) {                      // the parity path: the reciprocals the reference's divisions give
+        P.inv_mass = T(1) / P.mass;
+        P.inv_ixx = T(1) / P.ixx; P.inv_iyy = T(1) / P.iyy; P.inv_izz = T(1) / P.izz;
+    } else {
+        P.inv_mass = P.inv_mass * float(1.0 / ms);
+        P.inv_ixx = P.inv_ixx * float(1.0 / ixs); P.inv_iyy = P.inv_iyy * float(1.0 / iys); P.inv_izz = P.inv_izz * float(1.0 / izs);
+        P.pk_inv_i_pr = (fast::f32x2){ P.inv_ixx, P.inv_izz };
+    }
+    P.izz_m_iyy = P.izz - P.iyy; P.ixx_m_izz = P.ixx - P.izz; P.iyy_m_ixx = P.iyy - P.ixx;
+    P.half_rho = P.half_rho * T(rs);
+    P.half_rho_S = P.half_rho * P.S;
+}
+
 // ----- one evaluation of the equations of motion: simplified_6dof.py:333-503 ----------------------------
 // The fp64 parity form: the reference's operation order, every clamp and guard where the reference has it.
 // (The fp32-evaluation variants use dynamics_fast below.)
-template <typename T>
-FD_DEV void dynamics(const Params<T>& P, const Controls<T>& C, const T (&x)[FD_NX], T (&xd)[FD_NX])
+// WIND: the aerodynamic terms (:363-403) take the air-relative velocity v - R^T W (W = wind, NED); ug, vg, wg stay ground-relative.
+template <typename T, bool WIND = false>
+FD_DEV void dynamics(const Params<T>& P, const Controls<T>& C, const T (&x)[FD_NX], T (&xd)[FD_NX], const Wind<T>& wnd = Wind<T>{})
 {
     static_assert(sizeof(T) == 8, "fp32 evaluation goes through dynamics_fast");
-    const T u = x[3], v = x[4], w = x[5], theta = x[7];
+    const T ug = x[3], vg = x[4], wg = x[5], theta = x[7];
     const T p = x[9], q = x[10], r = x[11];
     T sin_phi, cos_phi, sin_theta, cos_theta, sin_psi, cos_psi;
     M<T>::sincos(x[6], sin_phi, cos_phi);
     M<T>::sincos(theta, sin_theta, cos_theta);
     M<T>::sincos(x[8], sin_psi, cos_psi);
+    T u = ug, v = vg, w = wg;
+    if constexpr (WIND) {
+        T bu, bv, bw;
+        body_wind<T>(sin_phi, cos_phi, sin_theta, cos_theta, sin_psi, cos_psi, wnd, bu, bv, bw);
+        u = ug - bu; v = vg - bv; w = wg - bw;
+    }
 
     const T airspeed = M<T>::sqrt(u * u + v * v + w * w);                               // :363
     const T safe_airspeed = pymax(airspeed, P.min_airspeed);                            // :364
@@ -462,13 +507,13 @@ FD_DEV void dynamics(const Params<T>& P, const Controls<T>& C, const T (&x)[FD_N
     const T n_moment = q_S * P.b * (P.cn_dr * C.dr_rad + P.damp_yaw * r * half_span_over_V + P.cn_beta * beta);
 
     const T sps = sin_phi * sin_theta, cps = cos_phi * sin_theta;                       // :440-452
-    xd[0] = cos_theta * cos_psi * u + (sps * cos_psi - cos_phi * sin_psi) * v + (cps * cos_psi + sin_phi * sin_psi) * w;
-    xd[1] = cos_theta * sin_psi * u + (sps * sin_psi + cos_phi * cos_psi) * v + (cps * sin_psi - sin_phi * cos_psi) * w;
-    xd[2] = -sin_theta * u + sin_phi * cos_theta * v + cos_phi * cos_theta * w;
+    xd[0] = cos_theta * cos_psi * ug + (sps * cos_psi - cos_phi * sin_psi) * vg + (cps * cos_psi + sin_phi * sin_psi) * wg;
+    xd[1] = cos_theta * sin_psi * ug + (sps * sin_psi + cos_phi * cos_psi) * vg + (cps * sin_psi - sin_phi * cos_psi) * wg;
+    xd[2] = -sin_theta * ug + sin_phi * cos_theta * vg + cos_phi * cos_theta * wg;
 
-    xd[3] = fx * P.inv_mass - q * w + r * v;                                            // :455-460
-    xd[4] = fy * P.inv_mass - r * u + p * w;
-    xd[5] = fz * P.inv_mass - p * v + q * u;
+    xd[3] = fx * P.inv_mass - q * wg + r * vg;                                          // :455-460
+    xd[4] = fy * P.inv_mass - r * ug + p * wg;
+    xd[5] = fz * P.inv_mass - p * vg + q * ug;
 
     const T theta_safe = clipv(theta, -P.max_pitch, P.max_pitch);                       // :463-471
     const T cos_ts = (theta_safe == theta) ? cos_theta : M<T>::cos(theta_safe);
@@ -560,12 +605,20 @@ __device__ unsigned fdyn_dbg_cnt[4096 * 8];
 // throughput-bound, a slow wave's issue gaps are filled by its neighbour): behind the wave-level branches -- measured at 1 Mi
 // envs 2.41e9 env-steps/s against 2.25e9 with the straight form.  The arithmetic is the same expression for expression: the
 // two forms are bit-equal (tests/test_gpu_parity_scale.py compares the two env builds).
-template <bool STRAIGHT = true>
+// WIND: as dynamics<double>; R^T W comes from the carried trigonometry (rebuilt first when it is stale), 15 VALU.
+template <bool STRAIGHT = true, bool WIND = false>
 FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, const float (&x)[FD_NX], Trig& tg, float dmax,
-                          float (&xd)[FD_NX])
+                          float (&xd)[FD_NX], const Wind<float>& wnd = Wind<float>{})
 {
-    const float u = x[3], v = x[4], w = x[5], theta = x[7];
+    const float ug = x[3], vg = x[4], wg = x[5], theta = x[7];
     const float p = x[9], q = x[10], r = x[11];
+    float u = ug, v = vg, w = wg;
+    if constexpr (WIND) {
+        if (FD_UNLIKELY(!(dmax <= 0.125f))) { tg = trig_of(x[6], theta, x[8]); dmax = 0.0f; }
+        float bu, bv, bw;
+        body_wind<float>(tg.phi.x, tg.phi.y, tg.th.x, tg.th.y, tg.psi.x, tg.psi.y, wnd, bu, bv, bw);
+        u = ug - bu; v = vg - bv; w = wg - bw;
+    }
 
     const fast::f32x2 vw = { v, w };
     const fast::f32x2 vw_sq = vw * vw;                                                      // v^2, w^2
@@ -665,9 +718,9 @@ FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, cons
 
     // :409-411 + :455-460   a = F/m + g-terms - omega x v
     const f32x2 g_cs = bc(P.g) * (tg.phi * bc(cth));                                        // g (cth sphi), g (cth cphi)
-    xd[3] = __builtin_fmaf(fxz.x + thrust, P.inv_mass, __builtin_fmaf(r, v, __builtin_fmaf(-q, w, -(P.g * sth))));
-    xd[4] = __builtin_fmaf(q_S * C.cy, P.inv_mass, __builtin_fmaf(p, w, __builtin_fmaf(-r, u, g_cs.x)));
-    xd[5] = __builtin_fmaf(-fxz.y, P.inv_mass, __builtin_fmaf(q, u, __builtin_fmaf(-p, v, g_cs.y)));
+    xd[3] = __builtin_fmaf(fxz.x + thrust, P.inv_mass, __builtin_fmaf(r, vg, __builtin_fmaf(-q, wg, -(P.g * sth))));
+    xd[4] = __builtin_fmaf(q_S * C.cy, P.inv_mass, __builtin_fmaf(p, wg, __builtin_fmaf(-r, ug, g_cs.x)));
+    xd[5] = __builtin_fmaf(-fxz.y, P.inv_mass, __builtin_fmaf(q, ug, __builtin_fmaf(-p, vg, g_cs.y)));
 
     // :416-431, :474-482  roll and yaw moments have one shape: packed as (l, n)
     const f32x2 hV = P.pk_half_b_c * bc(inv_V);                             // :416-417
@@ -685,14 +738,14 @@ FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, cons
     // :440-452 NED rates: Rz(psi) * [ (cth u + sth (sphi v + cphi w)), (cphi v - sphi w) ],  down = cth (sphi v + cphi w) - sth u
     // the plane rotations as packed pairs (the scalar form's products and FMAs, two per instruction):
     // (sv_cw, bh) = (sphi v + cphi w, cphi v - sphi w)
-    const fast::f32x2 sb = fast::pk_fma_bx_nhi(tg.phi, fast::lo_only(v), tg.phi.yx * fast::bc(w));
+    const fast::f32x2 sb = fast::pk_fma_bx_nhi(tg.phi, fast::lo_only(vg), tg.phi.yx * fast::bc(wg));
     const float sv_cw = sb.x;
-    const float ah = __builtin_fmaf(cth, u, sth * sv_cw);
+    const float ah = __builtin_fmaf(cth, ug, sth * sv_cw);
     // (north, east) = (cpsi ah - spsi bh, spsi ah + cpsi bh)
     const fast::f32x2 ne = fast::pk_fma_ayx_bx_nlo(tg.psi, fast::lo_only(ah), tg.psi * fast::bc(sb.y));
     xd[0] = ne.x;
     xd[1] = ne.y;
-    xd[2] = __builtin_fmaf(cth, sv_cw, -(sth * u));
+    xd[2] = __builtin_fmaf(cth, sv_cw, -(sth * ug));
 
     // :463-471 Euler rates with the clamped pitch:  (qr, theta_dot) = (sphi q + cphi r, cphi q - sphi r)
     const float inv_c = fast::rcp(cth_e);
@@ -774,9 +827,9 @@ struct FastRK {
 // the state; the storage type S sees ONE add per word per step (x += S(dt/6 * sum)) -- that add is what keeps the "mixed"
 // variant inside the 1e-4 gate.  The clamps / wraps of :256-291 are tested on the fp32 copy with one combined predicate and
 // the (rare) fix-up runs under a wave-level branch.
-template <typename S, bool STRAIGHT = true>
+template <typename S, bool STRAIGHT = true, bool WIND = false>
 FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Controls<float>& C, S (&x)[FD_NX], FastRK& f,
-                          float hdt, float fdt, float dt6)
+                          float hdt, float fdt, float dt6, const Wind<float>& wnd = Wind<float>{})
 {
     using T = float;
     // position (0..2) feeds nothing back, and roll / yaw enter only through their sin / cos: the stage states carry velocity,
@@ -803,16 +856,16 @@ FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Con
             }
         }
     };
-    dynamics_fast<STRAIGHT>(P, C, f.x0, f.t0, f.d0, k);                            // k1
+    dynamics_fast<STRAIGHT, WIND>(P, C, f.x0, f.t0, f.d0, k, wnd);                            // k1
     stage(hdt, T(1), true);
     T dm = trig_rotate_scaled(f.t0, hdt, k[6], k[7], k[8], tt);
-    dynamics_fast<STRAIGHT>(P, C, xt, tt, dm, k);                        // k2
+    dynamics_fast<STRAIGHT, WIND>(P, C, xt, tt, dm, k, wnd);                        // k2
     stage(hdt, T(2), false);
     dm = trig_rotate_scaled(f.t0, hdt, k[6], k[7], k[8], tt);
-    dynamics_fast<STRAIGHT>(P, C, xt, tt, dm, k);                        // k3
+    dynamics_fast<STRAIGHT, WIND>(P, C, xt, tt, dm, k, wnd);                        // k3
     stage(fdt, T(2), false);
     dm = trig_rotate_scaled(f.t0, fdt, k[6], k[7], k[8], tt);
-    dynamics_fast<STRAIGHT>(P, C, xt, tt, dm, k);                        // k4
+    dynamics_fast<STRAIGHT, WIND>(P, C, xt, tt, dm, k, wnd);                        // k4
     T ksum[FD_NX], inc[FD_NX];
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
@@ -891,8 +944,9 @@ FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Con
 // ----- Simplified6DOF.step x n_sub: RK4 + post-clamps, simplified_6dof.py:247-291 ------------------------
 // fp64 evaluation (T = double): the reference's operation order, every clamp applied every step.
 // fp32 evaluation (T = float): rk4_fast_step above.
-template <typename S, typename T, bool STRAIGHT = true>
-FD_DEV void rk4_substeps(const Params<T>& P, const Limits<S>& Lm, const Controls<T>& C, S (&x)[FD_NX], S dt, int n_sub)
+template <typename S, typename T, bool STRAIGHT = true, bool WIND = false>
+FD_DEV void rk4_substeps(const Params<T>& P, const Limits<S>& Lm, const Controls<T>& C, S (&x)[FD_NX], S dt, int n_sub,
+                         const Wind<T>& wnd = Wind<T>{})
 {
     if constexpr (sizeof(T) == 8) {
         for (int s = 0; s < n_sub; ++s) {
@@ -901,16 +955,16 @@ FD_DEV void rk4_substeps(const Params<T>& P, const Limits<S>& Lm, const Controls
             const T hdt = T(S(0.5) * dt), fdt = T(dt);
 #pragma unroll
             for (int i = 0; i < 12; ++i) xt[i] = T(x[i]);
-            dynamics<T>(P, C, xt, k);                                        // k1
+            dynamics<T, WIND>(P, C, xt, k, wnd);                                        // k1
 #pragma unroll
             for (int i = 0; i < 12; ++i) { acc[i] = S(k[i]); xt[i] = T(x[i] + S(hdt) * S(k[i])); }
-            dynamics<T>(P, C, xt, k);                                        // k2
+            dynamics<T, WIND>(P, C, xt, k, wnd);                                        // k2
 #pragma unroll
             for (int i = 0; i < 12; ++i) { acc[i] += S(2) * S(k[i]); xt[i] = T(x[i] + S(hdt) * S(k[i])); }
-            dynamics<T>(P, C, xt, k);                                        // k3
+            dynamics<T, WIND>(P, C, xt, k, wnd);                                        // k3
 #pragma unroll
             for (int i = 0; i < 12; ++i) { acc[i] += S(2) * S(k[i]); xt[i] = T(x[i] + S(fdt) * S(k[i])); }
-            dynamics<T>(P, C, xt, k);                                        // k4
+            dynamics<T, WIND>(P, C, xt, k, wnd);                                        // k4
             const S dt6 = dt / S(6);
 #pragma unroll
             for (int i = 0; i < 12; ++i) x[i] = x[i] + dt6 * (acc[i] + S(k[i]));              // :253
@@ -920,7 +974,7 @@ FD_DEV void rk4_substeps(const Params<T>& P, const Limits<S>& Lm, const Controls
         FastRK f;
         f.init(x);                                               // the ONLY full sincos of the launch (rare blocks aside)
         const T hdt = T(S(0.5) * dt), fdt = T(dt), dt6 = T(dt / S(6));
-        for (int s = 0; s < n_sub; ++s) rk4_fast_step<S, STRAIGHT>(P, Lm, C, x, f, hdt, fdt, dt6);
+        for (int s = 0; s < n_sub; ++s) rk4_fast_step<S, STRAIGHT, WIND>(P, Lm, C, x, f, hdt, fdt, dt6, wnd);
     }
 }
 

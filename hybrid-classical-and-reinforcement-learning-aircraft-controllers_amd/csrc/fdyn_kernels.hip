@@ -788,13 +788,94 @@ __device__ __forceinline__ void store_obs_tile(float* tile /*[64*19]*/, const fl
     __builtin_amdgcn_wave_barrier();
 }
 
-template <typename S, typename E>
+// ---- domain randomisation (the _dr entry points; DESIGN.md "Domain randomisation") ----------------------------------------
+// the env kernels take the randomisation arguments as a trailing pack: empty for the plain env, (dr, dr_consts) for the _dr one
+template <typename S> __device__ __forceinline__ void dr_unpack(S*& dr, const double*& drc, S* d, const double* c) { dr = d; drc = c; }
+// three standard normals from one Philox block (Box-Muller on its four words; fp32 transcendentals: statistical use only)
+__device__ __forceinline__ void dr_normals3(uint64_t seed, uint32_t env, uint32_t episode, uint32_t step, uint32_t word, float (&z)[3])
+{
+    Philox ph; uint32_t r[4];
+    ph.block(seed, env, episode, step, word, r);
+    const float m0 = fast::sqrt(-2.0f * __logf(u01(r[0]))), m1 = fast::sqrt(-2.0f * __logf(u01(r[2])));
+    float s0, c0, s1, c1;
+    fast::sincos(6.283185307179586f * u01(r[1]), s0, c0);
+    fast::sincos(6.283185307179586f * u01(r[3]), s1, c1);
+    z[0] = m0 * c0; z[1] = m0 * s0; z[2] = m1 * c1;
+}
+// air-relative body velocity of the stored state under the air-mass velocity W (NED), in the glue type A
+template <typename A, typename S>
+__device__ __forceinline__ void air_velocity(const S (&x)[FD_NX], const S (&W)[3], A& ua, A& va, A& wa)
+{
+    A sp, cp, st, ct, sy, cy, bu, bv, bw;
+    M<A>::sincos(A(x[6]), sp, cp); M<A>::sincos(A(x[7]), st, ct); M<A>::sincos(A(x[8]), sy, cy);
+    body_wind<A>(sp, cp, st, ct, sy, cy, Wind<A>{ A(W[0]), A(W[1]), A(W[2]) }, bu, bv, bw);
+    ua = A(x[3]) - bu; va = A(x[4]) - bv; wa = A(x[5]) - bw;
+}
+template <typename A, typename S>
+__device__ __forceinline__ A air_speed(const S (&x)[FD_NX], const S (&W)[3])
+{
+    A ua, va, wa;
+    air_velocity<A, S>(x, W, ua, va, wa);
+    return M<A>::sqrt(ua * ua + va * va + wa * wa);
+}
+// The randomisation part of a reset, after env_apply_reset has set x from the record: with FD_DC_REDRAW set, draw every row
+// from its range (Philox words FD_PHX_DR_RESET.. and FD_PHX_DR_GUST0, keyed like the record) and store it; otherwise read the
+// wind and gust the host left.  Then make the record's airspeed air-relative: v = (V0, 0, 0) + R^T (W + g0).  Returns W + g0.
+template <typename S>
+__device__ __forceinline__ void dr_reset(uint64_t seed, uint32_t env, uint32_t episode, const double* __restrict__ drc, double dt,
+                                         S* __restrict__ dr, int64_t n, int64_t i, S (&x)[FD_NX], S (&wair)[3])
+{
+    if (drc[FD_DC_REDRAW] != 0.0) {
+        Philox ph;
+        uint32_t r0[4], r1[4], r2[4];
+        ph.block(seed, env, episode, 0u, FD_PHX_DR_RESET, r0);
+        ph.block(seed, env, episode, 0u, FD_PHX_DR_RESET + 1, r1);
+        ph.block(seed, env, episode, 0u, FD_PHX_DR_RESET + 2, r2);
+        const uint32_t u[10] = { r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3], r2[0], r2[1] };
+        double v[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) {                    // range k = words 2k, 2k+1 of dr_consts; lo == hi gives lo exactly
+            const double lo = drc[2 * k], hi = drc[2 * k + 1];
+            v[k] = lo + (hi - lo) * double(u01(u[k]));
+        }
+        float sd, cd;
+        fast::sincos(float(v[1]), sd, cd);                // direction: an fp32 angle is plenty for a random draw
+        float z[3];
+        dr_normals3(seed, env, episode, 0u, FD_PHX_DR_GUST0, z);
+        const double V0 = double(x[3]);                   // the record's airspeed (x is still the still-air IC here)
+        const double sigma = v[3] * V0;                   // intensity x reset airspeed
+        const double a = exp(-dt * V0 / v[4]);            // first-order Gauss-Markov gust over one env step
+        const S row[FD_NDR] = { S(v[0] * double(cd)), S(v[0] * double(sd)), S(v[2]),
+                                S(sigma * double(z[0])), S(sigma * double(z[1])), S(sigma * double(z[2])),
+                                S(a), S(sigma * sqrt(1.0 - a * a)),
+                                S(v[5]), S(v[6]), S(v[7]), S(v[8]), S(v[9]) };
+#pragma unroll
+        for (int k = 0; k < FD_NDR; ++k) dr[k * n + i] = row[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) wair[k] = row[FD_DR_WIND_N + k] + row[FD_DR_GUST_N + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) wair[k] = dr[(FD_DR_WIND_N + k) * n + i] + dr[(FD_DR_GUST_N + k) * n + i];
+    }
+    S sp, cp, st, ct, sy, cy, bu, bv, bw;
+    M<S>::sincos(x[6], sp, cp); M<S>::sincos(x[7], st, ct); M<S>::sincos(x[8], sy, cy);
+    body_wind<S>(sp, cp, st, ct, sy, cy, Wind<S>{ wair[0], wair[1], wair[2] }, bu, bv, bw);
+    x[3] = x[3] + bu; x[4] = x[4] + bv; x[5] = x[5] + bw;
+}
+
+// DRA = {} : the plain env ; DRA = {S*, const double*} : the _dr entry points (dr rows, dr_consts).  A trailing parameter pack,
+// so that the plain instantiation keeps its argument list, kernarg layout and instructions.
+template <typename S, typename E, typename... DRA>
 __global__ void __launch_bounds__(FD_BLOCK)
 rate_env_reset_kernel(S* __restrict__ xs, E* __restrict__ es, int32_t* __restrict__ eis, float* __restrict__ pid_state,
                       const uint8_t* __restrict__ mask, const double* __restrict__ EC, const double* __restrict__ pool,
-                      int pool_depth, uint64_t seed, float* __restrict__ obs_out, int64_t n)
+                      int pool_depth, uint64_t seed, float* __restrict__ obs_out, int64_t n, DRA... dra)
 {
     __shared__ __attribute__((aligned(16))) float s_tile[FD_BLOCK / FD_WAVE][FD_WAVE * (FD_OBS_DIM + 1)];
+    constexpr bool DR = sizeof...(DRA) != 0;
+    S* dr = nullptr;
+    const double* drc = nullptr;
+    if constexpr (DR) dr_unpack(dr, drc, dra...);
     const LaneMap lm = lane_map(n);
     const int64_t i = lm.i;
     const int lane = lm.lane, wave = threadIdx.x / FD_WAVE;
@@ -808,11 +889,13 @@ rate_env_reset_kernel(S* __restrict__ xs, E* __restrict__ es, int32_t* __restric
     for (int k = 0; k < FD_OBS_DIM; ++k) o[k] = 0.0f;
     if (active) {
         const bool doit = mask ? mask[i] != 0 : true;
+        S wair[3];
         if (doit) {
             const int32_t episode = eis[FD_EI_EPISODE * n + i];
             S rec[FD_NR];
             fetch_reset_record<S>(pool, pool_depth, seed, i, episode, ec, rec);
             env_apply_reset<S, E>(rec, ec.cmd_type, x, e);
+            if constexpr (DR) dr_reset<S>(seed, uint32_t(i), uint32_t(episode), drc, EC[FD_EC_DT], dr, n, i, x, wair);
 #pragma unroll
             for (int k = 0; k < FD_NX; ++k) xs[k * n + i] = x[k];
             env_store<E>(e, es, n, i);
@@ -823,9 +906,14 @@ rate_env_reset_kernel(S* __restrict__ xs, E* __restrict__ es, int32_t* __restric
 #pragma unroll
             for (int k = 0; k < FD_NX; ++k) x[k] = xs[k * n + i];
             env_load<E>(e, es, n, i);
+            if constexpr (DR) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) wair[k] = dr[(FD_DR_WIND_N + k) * n + i] + dr[(FD_DR_GUST_N + k) * n + i];
+            }
         }
         S airspeed, altitude;
         airspeed_altitude<S>(x, airspeed, altitude);
+        if constexpr (DR) airspeed = air_speed<S, S>(x, wair);                   // the air-relative airspeed
         env_observation<S, S, E>(x, e, airspeed, altitude, o);
     }
     store_obs_tile(s_tile[wave], o, lane, obs_out, lm.wave_first, n);
@@ -859,7 +947,9 @@ extern "C" int fdyn_debug_read_counts(unsigned* out, int count, int clear)
 // OCC2: cap the registers at 256 so that two waves fit per SIMD.  At exactly one wave per SIMD (65 536 envs on 256 CUs) the
 // uncapped allocation (258 VGPRs) is 4 % faster; past that the second wave hides the first one's issue gaps
 // (1 Mi envs: 1.16e9 -> 1.56e9 env-steps/s).  The launcher picks by batch size; the arithmetic is the same.
-template <typename S, typename T, bool OCC2>
+// DR = true: the _dr entry points -- wind + gust in the aerodynamics, per-env parameter scales, the gust update and the
+// randomising resets (DESIGN.md "Domain randomisation").  DR = false is the plain env and compiles to its former instructions.
+template <typename S, typename T, bool OCC2, typename... DRA>
 __global__ void __launch_bounds__(FD_BLOCK, OCC2 ? 2 : 1)
 rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict__ es, int32_t* __restrict__ eis,
                      const uint8_t* __restrict__ type, const double* __restrict__ params, int n_types,
@@ -872,8 +962,12 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
                      float* __restrict__ obs_out /*[n][18]*/, float* __restrict__ reward_f32, S* __restrict__ reward_full,
                      uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated,
                      int32_t* __restrict__ ev_count, int32_t* __restrict__ ev_count_next, int32_t* __restrict__ ev_int,
-                     float* __restrict__ ev_flt, int ev_cap, int64_t n)
+                     float* __restrict__ ev_flt, int ev_cap, int64_t n, DRA... dra)
 {
+    constexpr bool DR = sizeof...(DRA) != 0;
+    S* dr = nullptr;
+    const double* drc = nullptr;
+    if constexpr (DR) dr_unpack(dr, drc, dra...);
     __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
     __shared__ __attribute__((aligned(16))) float s_tile[FD_BLOCK / FD_WAVE][FD_WAVE * (FD_OBS_DIM + 1)];
     __shared__ float s_pid_cfg[3 * FD_NPC];
@@ -911,6 +1005,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
     // (first touched by the accumulate at the end of sub-step 1) and the env words (touched after the 20 sub-steps) -- the second
     // half of the burst lands under the first sub-step instead of in front of it.
     S rec_pre[FD_NR];
+    S wair[3] = { S(0), S(0), S(0) }, dsc[5] = { S(1), S(1), S(1), S(1), S(1) };   // DR: air-mass velocity W + g, parameter scales
     const bool pre_drawn = !OCC2 && pool == nullptr && auto_reset != 0;
     // (fp32-evaluation builds only: in the fp64 build the split left a dead 20-byte private segment in the kernel descriptor --
     // never accessed, but a scratch set-up per launch -- and that build is the parity reference, not the benched one)
@@ -928,6 +1023,12 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
         step = eis[FD_EI_STEP * n + i];
         env_load<E>(e, es, n, i, uses_sched);
         if (pre_drawn) device_reset_record<S>(seed, uint32_t(i), uint32_t(episode), ec, rec_pre);
+        if constexpr (DR) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) wair[k] = dr[(FD_DR_WIND_N + k) * n + i] + dr[(FD_DR_GUST_N + k) * n + i];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) dsc[k] = dr[(FD_DR_MASS_S + k) * n + i];
+        }
     }
     if constexpr (EARLY_PARAMS) stage_params_finish<true>(s_params, spw, n_types);
     else stage_params<false>(s_params, params, n_types);
@@ -950,6 +1051,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
     if (active) {
         const double* blk = s_params + ty * FD_NP_STAGED;
         Params<T> P; P.load(blk);
+        if constexpr (DR) scale_params<T>(P, double(dsc[0]), double(dsc[1]), double(dsc[2]), double(dsc[3]), double(dsc[4]));
         Limits<S> Lm; Lm.load(blk);
 
         // ---- action: from the policy ([n][4] f32, one 16-B load per lane) or the fused rate PID -------------
@@ -998,7 +1100,8 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #endif
         FD_STAMP(1)
-        rk4_substeps<S, T, !OCC2>(P, Lm, C, x, dt_sub, ec.n_sub);
+        if constexpr (DR) rk4_substeps<S, T, !OCC2, true>(P, Lm, C, x, dt_sub, ec.n_sub, Wind<T>{ T(wair[0]), T(wair[1]), T(wair[2]) });
+        else rk4_substeps<S, T, !OCC2>(P, Lm, C, x, dt_sub, ec.n_sub);
         FD_STAMP(2)
         if constexpr (sizeof(E) == sizeof(S)) e.time += E(ec.dt);                 // :241-242 (the reference's accumulated sum)
         else e.time = E(S(step + 1) * ec.dt);                                     // fp32 env words: exact product, not an fp32 running sum
@@ -1037,12 +1140,28 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
             for (int k = 0; k < 3; ++k) e.cmd[k] = E(S(e.sched[k]) * sn);
         }
 
+        // ---- DR: gust update g <- A g + B n after the physics (first-order Gauss-Markov in NED); the observation, reward and
+        // stall test below see the air-mass velocity the next step flies in
+        if constexpr (DR) {
+            float z[3];
+            dr_normals3(seed, uint32_t(i), uint32_t(episode), uint32_t(step), FD_PHX_GUST, z);
+            const S ga = dr[FD_DR_GUST_A * n + i], gb = dr[FD_DR_GUST_B * n + i];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const S g = ga * dr[(FD_DR_GUST_N + k) * n + i] + gb * S(z[k]);
+                dr[(FD_DR_GUST_N + k) * n + i] = g;
+                wair[k] = dr[(FD_DR_WIND_N + k) * n + i] + g;
+            }
+        }
+
         // ---- reward, termination (rate_env.py:247-294,437-460) -------------------------------------------------
         // A = arithmetic type of the reward / observation glue: double in the fp64 parity variant, float where the
         // derivatives are evaluated in fp32 anyway (env_reward's header says why the settling timer is exempt)
         using A = typename GlueOf<S, T>::type;
         const A u_ = A(x[3]), v_ = A(x[4]), w_ = A(x[5]), roll_ = A(x[6]), pitch_ = A(x[7]);
-        const A airspeed = M<A>::sqrt(u_ * u_ + v_ * v_ + w_ * w_), altitude = -A(x[2]);      // simplified_6dof.py:295-331
+        A airspeed = M<A>::sqrt(u_ * u_ + v_ * v_ + w_ * w_);                                // simplified_6dof.py:295-331
+        if constexpr (DR) airspeed = air_speed<A, S>(x, wair);                               // DR: air-relative
+        const A altitude = -A(x[2]);
         const A err[3] = { A(e.cmd[0]) - A(x[9]), A(e.cmd[1]) - A(x[10]), A(e.cmd[2]) - A(x[11]) };
         const A aa[4] = { A(a[0]), A(a[1]), A(a[2]), A(a[3]) };
         A rew = env_reward<E, A>(e, err, aa, airspeed, altitude, roll_, pitch_, ec.dt, ec.settle_steps);
@@ -1093,6 +1212,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
                 fetch_reset_record<S>(pool, pool_depth, seed, i, episode, ec, rec);
             }
             env_apply_reset<S, E>(rec, ec.cmd_type, x, e);
+            if constexpr (DR) dr_reset<S>(seed, uint32_t(i), uint32_t(episode), drc, EC[FD_EC_DT], dr, n, i, x, wair);
             step = 0;
             episode += 1;
             // first observation of the new episode, in the glue type of this variant (an fp64 square root here is ~400 cycles
@@ -1103,6 +1223,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
             for (int k = 0; k < FD_NX; ++k) xa[k] = A0(x[k]);
             A0 airspeed, altitude;
             airspeed_altitude<A0>(xa, airspeed, altitude);
+            if constexpr (DR) airspeed = air_speed<A0, S>(x, wair);
             env_observation<S, A0, E>(x, e, airspeed, altitude, o);
             if (pid_mode) for (int k = 0; k < 3 * FD_NPS; ++k) pid_state[k * n + i] = 0.0f;   // pid_agent.reset()
         }
@@ -1334,5 +1455,58 @@ FD_DEFINE_CASCADE(fdyn_cascade_step_f32, float, float)
 FD_DEFINE_ENV(f64, double, double, double)
 FD_DEFINE_ENV(mixed, double, float, float)
 FD_DEFINE_ENV(f32, float, float, float)
+
+// the same two entry points with domain randomisation: + dr [FD_NDR][n] (state dtype), dr_consts [FD_NDC] fp64
+#define FD_DEFINE_ENV_DR(SUFFIX, S, E, T)                                                                    \
+    int fdyn_rate_env_reset_dr_##SUFFIX(S* x, E* e, int32_t* ei, float* pid_state, const uint8_t* mask,      \
+                                        const double* env_consts, const double* pool, int pool_depth,        \
+                                        uint64_t seed, float* obs_out, int64_t n, S* dr, const double* dr_consts, \
+                                        void* stream)                                                        \
+    {                                                                                                        \
+        if (!dr || !dr_consts) return FDYN_ERR_NULL;                                                         \
+        FD_CHECK_COMMON(n, 1)                                                                                \
+        if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;                                                \
+        hipLaunchKernelGGL((rate_env_reset_kernel<S, E, S*, const double*>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
+                           x, e, ei, pid_state, mask, env_consts, pool, pool_depth, seed, obs_out, n, dr, dr_consts); \
+        return launch_status();                                                                              \
+    }                                                                                                        \
+    int fdyn_rate_env_step_dr_##SUFFIX(S* x, E* e, int32_t* ei, const uint8_t* type, const double* params,   \
+                                       int n_types, const double* env_consts, const float* actions,          \
+                                       float* pid_state, const float* pid_cfg, const double* casc_consts,    \
+                                       float* actions_out, const S* rw_delta, const double* pool, int pool_depth, \
+                                       uint64_t seed, int auto_reset, float residual_scale, float* obs_out,  \
+                                       float* reward_f32,                                                    \
+                                       S* reward_full, uint8_t* terminated, uint8_t* truncated,              \
+                                       int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int,           \
+                                       float* ev_flt, int ev_cap, int64_t n, S* dr, const double* dr_consts, \
+                                       void* stream)                                                         \
+    {                                                                                                        \
+        if (!dr || !dr_consts) return FDYN_ERR_NULL;                                                         \
+        FD_CHECK_COMMON(n, n_types)                                                                          \
+        if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;                                                \
+        if ((!actions || residual_scale > 0.0f) && !(pid_state && pid_cfg && casc_consts)) return FDYN_ERR_NULL; \
+        if (!obs_out || !terminated || !truncated || !env_consts) return FDYN_ERR_NULL;                      \
+        if (ev_count && (!ev_int || !ev_flt)) return FDYN_ERR_NULL;                                          \
+        if (ev_count && (ev_cap < FD_EV_SHARDS || ev_cap % FD_EV_SHARDS != 0)) return FDYN_ERR_BAD_SIZE;       \
+        /* (the f64 build is never register-capped: no fp64 OCC2 instantiation of the randomised kernel) */        \
+        if (sizeof(T) == 4 && n > int64_t(simd_count()) * FD_WAVE)   /* more than one wave per SIMD */            \
+            hipLaunchKernelGGL((rate_env_step_kernel<S, T, (sizeof(T) == 4), S*, const double*>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
+                           x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg,         \
+                           casc_consts, actions_out, rw_delta, pool, pool_depth, seed, auto_reset,           \
+                           residual_scale, obs_out,                                                          \
+                           reward_f32, reward_full, terminated, truncated, ev_count, ev_count_next, ev_int, ev_flt,  \
+                           ev_cap, n, dr, dr_consts);                                                   \
+        else                                                                                                 \
+            hipLaunchKernelGGL((rate_env_step_kernel<S, T, false, S*, const double*>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
+                           x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg,         \
+                           casc_consts, actions_out, rw_delta, pool, pool_depth, seed, auto_reset,           \
+                           residual_scale, obs_out,                                                          \
+                           reward_f32, reward_full, terminated, truncated, ev_count, ev_count_next, ev_int, ev_flt,  \
+                           ev_cap, n, dr, dr_consts);                                                   \
+        return launch_status();                                                                              \
+    }
+FD_DEFINE_ENV_DR(f64, double, double, double)
+FD_DEFINE_ENV_DR(mixed, double, float, float)
+FD_DEFINE_ENV_DR(f32, float, float, float)
 
 }  // extern "C"

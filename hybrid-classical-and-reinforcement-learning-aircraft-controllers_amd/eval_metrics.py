@@ -203,22 +203,24 @@ class EpisodeRecorder:
         return calc.compute_batch(self.times, self.rates, self.commands, self.actions, self.rewards, self.lengths)
 
 
-def _make_env(n_episodes, difficulty, episode_length, command_type, seed, precision, sampling, dt):
+def _make_env(n_episodes, difficulty, episode_length, command_type, seed, precision, sampling, dt, disturbances=None):
     from .rate_env import GpuRateVecEnv
     return GpuRateVecEnv(n_episodes, difficulty, episode_length, dt, command_type, seed=seed, precision=precision,
-                         sampling=sampling)
+                         sampling=sampling, disturbances=disturbances)
 
 
 @torch.no_grad()
 def evaluate_pid_controller(n_episodes: int = 10, difficulty: str = "medium", episode_length: float = 10.0,
                             command_type: str = "step", seed: Optional[int] = None, precision: str = "mixed",
                             sampling: str = "device", dt: float = 0.02, throttle: float = 0.5,
-                            pid_dt: Optional[float] = None, return_recorder: bool = False):
+                            pid_dt: Optional[float] = None, return_recorder: bool = False, disturbances=None):
     """eval_rate.py:129-235: the rate PID (default gains) flies every episode; rates and command are sampled BEFORE each
     step, time after it (:190-222); throttle 0.5 (:196); `compute_action` is called without dt (:200), so the PIDs see
     ControllerConfig.rate_loop_dt (rate_agent.py:103) -- pass pid_dt=dt for a PID told the true step.
+    `disturbances`: fly under domain randomisation (a Disturbances or a `domain_randomization:` mapping; same seed => the
+    same wind, gusts and airframes as evaluate_learned_controller draws).
     Returns (metrics [FD_NM, N] float64 on the device, aggregated RateControlMetrics)."""
-    env = _make_env(n_episodes, difficulty, episode_length, command_type, seed, precision, sampling, dt)
+    env = _make_env(n_episodes, difficulty, episode_length, command_type, seed, precision, sampling, dt, disturbances)
     env.casc_consts = torch.as_tensor(
         cascade_consts(pid_throttle=throttle, pid_dt=ControllerConfig().rate_loop_dt if pid_dt is None else pid_dt),
         device=env.device)
@@ -238,11 +240,12 @@ def evaluate_pid_controller(n_episodes: int = 10, difficulty: str = "medium", ep
 def evaluate_learned_controller(policy, n_episodes: int = 10, difficulty: str = "medium", episode_length: float = 10.0,
                                 command_type: str = "step", deterministic: bool = True, seed: Optional[int] = None,
                                 precision: str = "mixed", sampling: str = "device", dt: float = 0.02,
-                                return_recorder: bool = False):
+                                return_recorder: bool = False, disturbances=None):
     """eval_rate.py:25-126: the policy flies every episode (recurrent state zeroed at the start, :84-86); rates and
     command are sampled AFTER each step (:101-106); the recorded action is the policy's output clipped to the action
-    space, as SB3's `predict` returns it.  `policy`: a `RateLSTMPolicy` (already on the device)."""
-    env = _make_env(n_episodes, difficulty, episode_length, command_type, seed, precision, sampling, dt)
+    space, as SB3's `predict` returns it.  `policy`: a `RateLSTMPolicy` (already on the device).  `disturbances`: as
+    evaluate_pid_controller."""
+    env = _make_env(n_episodes, difficulty, episode_length, command_type, seed, precision, sampling, dt, disturbances)
     T = int(episode_length / dt)
     rec = EpisodeRecorder(env, T)
     obs = env.reset()

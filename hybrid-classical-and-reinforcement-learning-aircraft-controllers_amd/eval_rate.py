@@ -45,11 +45,21 @@ def main(argv=None):
     ap.add_argument("--pid-only", action="store_true")
     ap.add_argument("--pid-true-dt", action="store_true",
                     help="give the PID the env dt instead of ControllerConfig.rate_loop_dt (what eval_rate.py:200 does)")
+    ap.add_argument("--domain-randomization", type=str, default=None, metavar="PATH",
+                    help="fly under the `domain_randomization:` section of this YAML (PID and policy see the same draws)")
     a = ap.parse_args(argv)
     if not a.pid_only and a.model is None:
         ap.error("--model is required (or --pid-only)")
     kw = dict(n_episodes=a.n_episodes, difficulty=a.difficulty, episode_length=a.episode_length,
               command_type=a.command_type, seed=a.seed, precision=a.precision)
+    if a.domain_randomization:
+        import yaml
+        with open(a.domain_randomization) as f:
+            dr = yaml.safe_load(f).get("domain_randomization")
+        if dr is None:
+            ap.error(f"{a.domain_randomization} has no domain_randomization: section")
+        kw["disturbances"] = dr
+        print(f"Domain randomisation: {dr}")
     learned_avg = None
     if not a.pid_only:
         print(f"\nEvaluating Learned Controller: {a.model}")

@@ -26,7 +26,8 @@ class GpuRateVecEnv:
                  command_type: str = "step", seed: Optional[int] = None, precision: str = "mixed",
                  sampling: str = "device", pool_depth: int = 8, types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, event_capacity: Optional[int] = None,
-                 numpy_io: bool = False, device=None, residual_scale: float = 0.0, sensor_noise: Optional[dict] = None):
+                 numpy_io: bool = False, device=None, residual_scale: float = 0.0, sensor_noise: Optional[dict] = None,
+                 disturbances=None):
         self.lib = _lib.load()
         self.device = device or _lib.require_gpu()
         self.num_envs = self.n = int(num_envs)
@@ -89,13 +90,40 @@ class GpuRateVecEnv:
         self._reset_fn = getattr(self.lib, f"fdyn_rate_env_reset_{precision}")
         self._step_fn = getattr(self.lib, f"fdyn_rate_env_step_{precision}")
         self._pending = None
+        # optional domain randomisation (wind, gusts, per-env mass / inertia / air density; disturbances.py): None keeps the
+        # plain entry points and allocates nothing
+        self.dr, self.dr_consts, self.disturbances = None, None, None
+        if disturbances is not None:
+            self.set_disturbances(disturbances)
+
+    def set_disturbances(self, d):
+        """Swap the randomisation ranges (a Disturbances or a `domain_randomization:` mapping); each env draws from them at its
+        next reset.  The first call switches the env to the _dr entry points: dr [FD_NDR][N] (state dtype, FD_DR_* rows) is
+        readable and writable between steps.  An env built without disturbances cannot take them later in a captured graph."""
+        from .disturbances import Disturbances, as_disturbances, neutral_rows
+        d = as_disturbances(d)
+        if d is None:
+            d = Disturbances()                       # neutral ranges: still air, unit multipliers
+        self.disturbances = d
+        blk = torch.as_tensor(d.block(), device=self.device)
+        if self.dr_consts is None:
+            self.dr_consts = blk
+            self.dr = torch.as_tensor(neutral_rows(self.n), device=self.device).to(self.dtype).contiguous()
+            self._reset_fn = getattr(self.lib, f"fdyn_rate_env_reset_dr_{self.precision}")
+            self._step_fn = getattr(self.lib, f"fdyn_rate_env_step_dr_{self.precision}")
+        else:
+            self.dr_consts.copy_(blk)                # in place: a captured graph keeps reading the same block
+        return d
+
+    def _dr_args(self):
+        return () if self.dr is None else (_lib.ptr(self.dr), _lib.ptr(self.dr_consts))
 
     # ---- vec-env surface ------------------------------------------------------------------------------------
     def reset(self, mask: Optional[torch.Tensor] = None):
         m = None if mask is None else mask.to(torch.uint8).contiguous()
         rc = self._reset_fn(_lib.ptr(self.x), _lib.ptr(self.e), _lib.ptr(self.ei), _lib.ptr(self.pid_state),
                             _lib.ptr(m), _lib.ptr(self.env_consts), _lib.ptr(self.pool), self.pool_depth,
-                            self.seed_value, _lib.ptr(self.obs), self.n, _lib.current_stream())
+                            self.seed_value, _lib.ptr(self.obs), self.n, *self._dr_args(), _lib.current_stream())
         _lib.check(rc, "RateControlEnv.reset")
         if self.sensor is not None:
             if m is None:
@@ -127,7 +155,7 @@ class GpuRateVecEnv:
                            self.seed_value, int(auto_reset), self.residual_scale, _lib.ptr(self.obs), _lib.ptr(self.rewards),
                            _lib.ptr(self.rewards_full), _lib.ptr(self.terminated), _lib.ptr(self.truncated),
                            cur.data_ptr(), nxt.data_ptr(), _lib.ptr(self.ev_int), _lib.ptr(self.ev_flt), self.ev_cap,
-                           self.n, _lib.current_stream())
+                           self.n, *self._dr_args(), _lib.current_stream())
         _lib.check(rc, "RateControlEnv.step")
         if self.sensor is not None:
             mask = None

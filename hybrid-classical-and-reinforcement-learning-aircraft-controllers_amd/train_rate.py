@@ -15,7 +15,7 @@ import torch.distributed as dist
 from .policy import RateLSTMPolicy
 from .ppo import PPOConfig, RecurrentPPO
 from .training_utils import (behavior_cloning_pretrain, collect_pid_demonstrations, create_callbacks, create_vec_env, load_config,
-                             normalize_config,
+                             normalize_config, phase_disturbances,
                              run_final_evaluation)
 
 DEFAULT_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs", "training", "ppo_lstm.yaml")
@@ -117,6 +117,9 @@ def main(argv=None):
             config["environment"]["difficulty"] = phase["difficulty"]
             config["environment"]["command_type"] = phase["command_type"]
             env = create_vec_env(config, n_envs=n_envs, seed=seed + rank * n_envs, precision=args.precision)
+            dr = phase_disturbances(config, phase)          # a phase's own domain_randomization block replaces the top-level one
+            if dr is not None:
+                env.set_disturbances(dr)
             model.set_env(env)
             if callback is not None:                        # train_rate.py:163-167: callbacks rebuilt on the phase's task
                 callback = create_callbacks(config, previous=callback)

@@ -75,7 +75,14 @@ def create_vec_env(config: dict, n_envs: int = 4, seed: Optional[int] = None, **
     """training_utils.py:49-69: same arguments; returns ONE device-resident vec-env instead of n_envs subprocesses.
     Env `i` is seeded `seed + i` like `make_env(config, rank=i, seed)` (:41)."""
     e = config["environment"]
+    if config.get("domain_randomization") is not None:      # the optional `domain_randomization:` section (disturbances.py)
+        kw.setdefault("disturbances", config["domain_randomization"])
     return GpuRateVecEnv(n_envs, e["difficulty"], e["episode_length"], e["dt"], e["command_type"], seed=seed, **kw)
+
+
+def phase_disturbances(config: dict, phase: dict):
+    """The `domain_randomization:` block a curriculum phase flies under: its own, else the top-level one (None: none)."""
+    return phase.get("domain_randomization", config.get("domain_randomization"))
 
 
 def collect_pid_demonstrations(n_episodes: int = 100, difficulty: str = "medium", save_path: Optional[str] = None,

@@ -190,6 +190,48 @@ FDYN_DECLARE_ENV(f64, double, double)
 FDYN_DECLARE_ENV(mixed, double, float)       /* fp32 env words: see fdyn_layout.h, FD_E_* */
 FDYN_DECLARE_ENV(f32, float, float)
 
+/* ---- rate-control env with domain randomisation (design_docs/06_RL_AGENT_TRAINING.md "Domain Randomization") ------------------
+ * The two entry points above plus dr [FD_NDR][n] in the state dtype (FD_DR_* rows) and dr_consts [FD_NDC] fp64 (FD_DC_* ranges);
+ * NULL for either => FDYN_ERR_NULL.  In the dynamics the aerodynamics see the air-relative body velocity v - R^T (W + g)
+ * (W = steady wind, g = gust, NED, both read from dr and held over the step), kinematics keep the ground-relative one, and the
+ * type's mass, inertias and air density are multiplied by the env's FD_DR_*_S rows.  After the physics the gust advances as
+ * g <- A g + B n (n ~ N(0, 1) per axis, Philox keyed by seed, env, episode, step).  Observation airspeed, the airspeed
+ * stability reward term and the stall test use the air-relative airspeed.  A reset with dr_consts[FD_DC_REDRAW] != 0 draws
+ * every row from its range (A = exp(-dt V0 / L), B = sigma sqrt(1 - A^2), g0 ~ N(0, sigma^2), sigma = intensity V0, V0 = the
+ * record's airspeed); with 0 it keeps the rows.  Either way the record's airspeed is air-relative: v = (V0, 0, 0) + R^T (W + g0).
+ * IC and command draws are those of the plain entry points.  With neutral ranges (no wind, intensity 0, every scale 1) the
+ * results equal the plain entry points' bit for bit.                                                                              */
+int fdyn_rate_env_reset_dr_f64(double* x, double* e, int32_t* ei, float* pid_state, const uint8_t* mask, const double* env_consts,
+                               const double* pool, int pool_depth, uint64_t seed, float* obs_out, int64_t n, double* dr,
+                               const double* dr_consts, void* stream);
+int fdyn_rate_env_step_dr_f64(double* x, double* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+                              const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg,
+                              const double* casc_consts, float* actions_out, const double* rw_delta, const double* pool,
+                              int pool_depth, uint64_t seed, int auto_reset, float residual_scale, float* obs_out,
+                              float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated, int32_t* ev_count,
+                              int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, double* dr,
+                              const double* dr_consts, void* stream);
+int fdyn_rate_env_reset_dr_mixed(double* x, float* e, int32_t* ei, float* pid_state, const uint8_t* mask, const double* env_consts,
+                                 const double* pool, int pool_depth, uint64_t seed, float* obs_out, int64_t n, double* dr,
+                                 const double* dr_consts, void* stream);
+int fdyn_rate_env_step_dr_mixed(double* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+                                const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg,
+                                const double* casc_consts, float* actions_out, const double* rw_delta, const double* pool,
+                                int pool_depth, uint64_t seed, int auto_reset, float residual_scale, float* obs_out,
+                                float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated, int32_t* ev_count,
+                                int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, double* dr,
+                                const double* dr_consts, void* stream);
+int fdyn_rate_env_reset_dr_f32(float* x, float* e, int32_t* ei, float* pid_state, const uint8_t* mask, const double* env_consts,
+                               const double* pool, int pool_depth, uint64_t seed, float* obs_out, int64_t n, float* dr,
+                               const double* dr_consts, void* stream);
+int fdyn_rate_env_step_dr_f32(float* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+                              const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg,
+                              const double* casc_consts, float* actions_out, const float* rw_delta, const double* pool,
+                              int pool_depth, uint64_t seed, int auto_reset, float residual_scale, float* obs_out,
+                              float* reward_f32, float* reward_full, uint8_t* terminated, uint8_t* truncated, int32_t* ev_count,
+                              int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, float* dr,
+                              const double* dr_consts, void* stream);
+
 /* ---- policy-side fused kernels (csrc/policy_kernels.hip) ------------------------------------------------------------
  * LSTM cell point-wise update from pre-activation gates [B][4H] (PyTorch order i,f,g,o; bias already added by the
  * GEMM): replaces the ~40 element-wise launches torch needs per cell (nn.LSTM arithmetic used by

@@ -138,6 +138,32 @@ enum { FD_EV_ENV = 0, FD_EV_LENGTH, FD_EV_TERMINATED, FD_EV_NI = 3 };           
  * cap_s = ev_cap / FD_EV_SHARDS; size ev_cap with fdyn_event_capacity(n) to never lose a record.                  */
 enum { FD_EV_SHARDS = 64 };
 
+/* ---- domain randomisation of the rate env (fdyn_rate_env_{reset,step}_dr_*), design_docs/06_RL_AGENT_TRAINING.md ---------
+ * per-env disturbance rows dr [FD_NDR][n] in the state dtype: steady wind and gust state in NED (m/s; the air-mass velocity is
+ * their sum), the per-episode coefficients of the gust update g <- A g + B n (n ~ N(0, 1) per axis), and multipliers on the
+ * type's mass, inertias and air density                                                                                      */
+enum {
+    FD_DR_WIND_N = 0, FD_DR_WIND_E, FD_DR_WIND_D,
+    FD_DR_GUST_N, FD_DR_GUST_E, FD_DR_GUST_D,
+    FD_DR_GUST_A, FD_DR_GUST_B,
+    FD_DR_MASS_S, FD_DR_IXX_S, FD_DR_IYY_S, FD_DR_IZZ_S, FD_DR_RHO_S,
+    FD_NDR = 13
+};
+/* ranges the resets draw the rows from (fp64, lo / hi pairs): wind speed (m/s) and direction (rad, the NED heading the air
+ * moves toward), vertical wind (m/s, positive down), turbulence intensity (gust sigma as a fraction of the reset airspeed), gust
+ * length scale L (m), the five multipliers; FD_DC_REDRAW = 1: every reset draws the rows, 0: resets keep what is there        */
+enum {
+    FD_DC_WIND_SPEED_LO = 0, FD_DC_WIND_SPEED_HI, FD_DC_WIND_DIR_LO, FD_DC_WIND_DIR_HI, FD_DC_WIND_VERT_LO, FD_DC_WIND_VERT_HI,
+    FD_DC_TURB_LO, FD_DC_TURB_HI, FD_DC_GUST_L_LO, FD_DC_GUST_L_HI,
+    FD_DC_MASS_LO, FD_DC_MASS_HI, FD_DC_IXX_LO, FD_DC_IXX_HI, FD_DC_IYY_LO, FD_DC_IYY_HI, FD_DC_IZZ_LO, FD_DC_IZZ_HI,
+    FD_DC_RHO_LO, FD_DC_RHO_HI,
+    FD_DC_REDRAW,
+    FD_NDC = 21
+};
+/* Philox counter words (fourth counter word; the first three are env, episode, step) of the randomisation draws -- the IC and
+ * command draws use 0..3 and the random-walk command 7                                                                       */
+enum { FD_PHX_DR_RESET = 16, FD_PHX_DR_GUST0 = 19, FD_PHX_GUST = 20 };
+
 /* ---- per-episode evaluation metrics, learned_controllers/eval/metrics.py:8-40 (field order of RateControlMetrics) */
 enum {
     FD_M_SETTLE_ROLL = 0, FD_M_SETTLE_PITCH, FD_M_SETTLE_YAW,          /* s                           */
