@@ -15,6 +15,7 @@ _i, _i64, _u64, _d, _f = C.c_int, C.c_int64, C.c_uint64, C.c_double, C.c_float
 
 _SIXDOF = [_p, _p, _p, _p, _i, _i64, _d, _i, _p, _p]
 _CASCADE = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
+_AGENT = [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]
 _HYBRID = [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i64, _d, _p]
 _ENV_RESET = [_p, _p, _p, _p, _p, _p, _p, _i, _u64, _p, _i64, _p]
 _ENV_STEP = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _u64, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p,
@@ -51,9 +52,7 @@ SIGNATURES = {
     "fdyn_episode_flags": (_i, [_p, _p, _p, _p, _p, _i64, _p]),
     "fdyn_policy_trunks": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "fdyn_policy_trunks_heads": (_i, [_p] * 11 + [_u64, _p, _i, _p, _p, _p, _i64, _p]),
-    "fdyn_agent_step_f64": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]),
-    "fdyn_agent_step_mixed": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]),
-    "fdyn_agent_step_f32": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]),
+    "fdyn_agent_step_f64": (_i, _AGENT), "fdyn_agent_step_mixed": (_i, _AGENT), "fdyn_agent_step_f32": (_i, _AGENT),
     "fdyn_hybrid_step_f64": (_i, _HYBRID), "fdyn_hybrid_step_mixed": (_i, _HYBRID), "fdyn_hybrid_step_f32": (_i, _HYBRID),
     "fdyn_colsum_ws_floats": (_i64, [_i64, _i, _i64, _i]),
     "fdyn_colsum": (_i, [_p, _i, _i64, _i, _i64, _i, _p, _p, _p]),
@@ -62,8 +61,6 @@ SIGNATURES = {
     "fdyn_lstm_cell_mfma_inplace_ok": (_i, [_i, _i, _i, _i64]),
     "fdyn_lstm_cell_mfma_pair": (_i, [_p, _i, _p, _i, _i64, _i] + [_p] * 13),
     "fdyn_lstm_cell_mfma_train": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i, _p]),
-    "fdyn_policy_recurrent_image_bytes": (_i, []),
-    "fdyn_policy_recurrent": (_i, [_p] * 12 + [_i64, _p]),
     "fdyn_policy_features_image_bytes": (_i, []),
     "fdyn_policy_features": (_i, [_p, _p, _p, _p, _i64, _p]),
     "fdyn_policy_features_flags": (_i, [_p] * 9 + [_i64, _p]),
@@ -97,7 +94,7 @@ def load():
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
-        if lib.fdyn_abi_version() != 2:
+        if lib.fdyn_abi_version() != 3:
             raise FdynError("libfdyn_hip.so ABI version mismatch")
         _lib = lib
     return _lib

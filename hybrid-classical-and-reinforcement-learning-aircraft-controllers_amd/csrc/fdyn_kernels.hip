@@ -1259,8 +1259,6 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
 // =========================================================================================================
 // C-ABI (include/fdyn.h)
 // =========================================================================================================
-static inline unsigned grid_for(int64_t n) { return unsigned((n + FD_BLOCK - 1) / FD_BLOCK); }
-
 static int g_simds = 0;
 static int simd_count()
 {
@@ -1270,12 +1268,68 @@ static int simd_count()
     }
     return g_simds;
 }
-static inline int launch_status() { return int(hipGetLastError()); }
+
+// every kernel of this file is launched the same way: one lane per row, FD_BLOCK lanes per workgroup, no dynamic LDS
+template <typename K, typename... A>
+static int launch(K kernel, int64_t n, void* stream, A... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(unsigned((n + FD_BLOCK - 1) / FD_BLOCK)), dim3(FD_BLOCK), 0, (hipStream_t)stream, args...);
+    return int(hipGetLastError());
+}
 
 #define FD_CHECK_COMMON(n, n_types)                                       \
     if ((n) < 0 || (n) > (int64_t(1) << 31) - FD_BLOCK) return FDYN_ERR_BAD_SIZE;   \
     if ((n_types) < 1 || (n_types) > FD_MAX_TYPES) return FDYN_ERR_BAD_TYPES;       \
     if ((n) == 0) return FDYN_OK;
+
+// simplified_6dof.py:241-245: dt <= min_timestep or > max_timestep raises ValueError (defaults)
+static inline bool bad_dt(double dt) { return !(dt > 1e-6) || dt > 1.0; }
+
+// The rate env's reset and step, plain and with domain randomisation (DRA = S* dr [FD_NDR][n], const double* dr_consts [FD_NDC]):
+// the parameters they share are spelled once, the entry points below forward to one host function each.
+#define FD_ENV_RESET_PARAMS(S, E)                                                                            \
+    S* x, E* e, int32_t* ei, float* pid_state, const uint8_t* mask, const double* env_consts, const double* pool, \
+    int pool_depth, uint64_t seed, float* obs_out, int64_t n
+#define FD_ENV_RESET_ARGS x, e, ei, pid_state, mask, env_consts, pool, pool_depth, seed, obs_out, n
+#define FD_ENV_STEP_PARAMS(S, E)                                                                             \
+    S* x, E* e, int32_t* ei, const uint8_t* type, const double* params, int n_types, const double* env_consts, \
+    const float* actions, float* pid_state, const float* pid_cfg, const double* casc_consts, float* actions_out, \
+    const S* rw_delta, const double* pool, int pool_depth, uint64_t seed, int auto_reset, float residual_scale, \
+    float* obs_out, float* reward_f32, S* reward_full, uint8_t* terminated, uint8_t* truncated, int32_t* ev_count, \
+    int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n
+#define FD_ENV_STEP_ARGS                                                                                     \
+    x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg, casc_consts, actions_out, rw_delta, pool, \
+    pool_depth, seed, auto_reset, residual_scale, obs_out, reward_f32, reward_full, terminated, truncated, ev_count, \
+    ev_count_next, ev_int, ev_flt, ev_cap, n
+
+template <typename S, typename E, typename... DRA>
+static int env_reset(FD_ENV_RESET_PARAMS(S, E), void* stream, DRA... dra)
+{
+    if ((... || !dra)) return FDYN_ERR_NULL;
+    FD_CHECK_COMMON(n, 1)
+    if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;
+    return launch(rate_env_reset_kernel<S, E, DRA...>, n, stream, FD_ENV_RESET_ARGS, dra...);
+}
+
+template <typename S, typename E, typename T, typename... DRA>
+static int env_step(FD_ENV_STEP_PARAMS(S, E), void* stream, DRA... dra)
+{
+    if ((... || !dra)) return FDYN_ERR_NULL;
+    FD_CHECK_COMMON(n, n_types)
+    if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;
+    if ((!actions || residual_scale > 0.0f) && !(pid_state && pid_cfg && casc_consts)) return FDYN_ERR_NULL;
+    if (!obs_out || !terminated || !truncated || !env_consts) return FDYN_ERR_NULL;
+    if (ev_count && (!ev_int || !ev_flt)) return FDYN_ERR_NULL;
+    // records go to FD_EV_SHARDS equal segments: a capacity that is not a positive multiple would give segments of zero (or
+    // fewer than stated) records and drop episode ends silently
+    if (ev_count && (ev_cap < FD_EV_SHARDS || ev_cap % FD_EV_SHARDS != 0)) return FDYN_ERR_BAD_SIZE;
+    // fp32 arithmetic and more than one wave per SIMD: the register-capped build, two workgroups per CU (the f64 build is
+    // never register-capped: its flag is false on both sides, no fp64 OCC2 instantiation)
+    constexpr bool FP32 = sizeof(T) == 4;
+    const bool occ2 = FP32 && n > int64_t(simd_count()) * FD_WAVE;
+    return launch(occ2 ? rate_env_step_kernel<S, T, FP32, DRA...> : rate_env_step_kernel<S, T, false, DRA...>, n, stream,
+                  FD_ENV_STEP_ARGS, dra...);
+}
 
 extern "C" {
 
@@ -1315,11 +1369,8 @@ int fdyn_device_info(int* cu_count, int* wave_size, char* arch, int arch_len)
         FD_CHECK_COMMON(n, n_types)                                                                          \
         if (n_sub < 1) return FDYN_ERR_BAD_SIZE;                                                             \
         const double dt_sub = dt / n_sub;                                                                    \
-        /* simplified_6dof.py:241-245: dt <= min_timestep or > max_timestep raises ValueError (defaults) */ \
-        if (!(dt_sub > 1e-6) || dt_sub > 1.0) return FDYN_ERR_BAD_DT;                                        \
-        hipLaunchKernelGGL((sixdof_step_kernel<S, T>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, u, type, params, n_types, n, S(dt_sub), n_sub, derived_out);              \
-        return launch_status();                                                                              \
+        if (bad_dt(dt_sub)) return FDYN_ERR_BAD_DT;                                                          \
+        return launch(sixdof_step_kernel<S, T>, n, stream, x, u, type, params, n_types, n, S(dt_sub), n_sub, derived_out); \
     }
 FD_DEFINE_SIXDOF(fdyn_sixdof_step_f64, double, double)
 FD_DEFINE_SIXDOF(fdyn_sixdof_step_mixed, double, float)
@@ -1328,23 +1379,19 @@ FD_DEFINE_SIXDOF(fdyn_sixdof_step_f32, float, float)
 int fdyn_derived_f64(const double* x, int64_t n, double* out, void* stream)
 {
     FD_CHECK_COMMON(n, 1)
-    hipLaunchKernelGGL((derived_kernel<double>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, x, n, out);
-    return launch_status();
+    return launch(derived_kernel<double>, n, stream, x, n, out);
 }
 int fdyn_derived_f32(const float* x, int64_t n, float* out, void* stream)
 {
     FD_CHECK_COMMON(n, 1)
-    hipLaunchKernelGGL((derived_kernel<float>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, x, n, out);
-    return launch_status();
+    return launch(derived_kernel<float>, n, stream, x, n, out);
 }
 
 int fdyn_pid_compute_batch(const float* cfg, int cfg_per_lane, float* state, const float* setpoint,
                            const float* measurement, float dt, float* out, int64_t n, void* stream)
 {
     FD_CHECK_COMMON(n, 1)
-    hipLaunchKernelGGL(pid_batch_kernel, dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, cfg, cfg_per_lane,
-                       state, setpoint, measurement, dt, out, n);
-    return launch_status();
+    return launch(pid_batch_kernel, n, stream, cfg, cfg_per_lane, state, setpoint, measurement, dt, out, n);
 }
 
 #define FD_DEFINE_CASCADE(NAME, S, T)                                                                        \
@@ -1354,11 +1401,9 @@ int fdyn_pid_compute_batch(const float* cfg, int cfg_per_lane, float* state, con
     {                                                                                                        \
         FD_CHECK_COMMON(n, n_types)                                                                          \
         if (n_wp < 1 || n_wp > FD_MAX_WAYPOINTS || n_steps < 0) return FDYN_ERR_BAD_SIZE;                    \
-        if (!(dt > 1e-6) || dt > 1.0) return FDYN_ERR_BAD_DT;                                                \
-        hipLaunchKernelGGL((cascade_step_kernel<S, T>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, pid_state, wp_idx, type, params, n_types, pid_cfg, consts, wps, n_wp, n, S(dt), \
-                           n_steps, surf_out, reached_total);                                           \
-        return launch_status();                                                                              \
+        if (bad_dt(dt)) return FDYN_ERR_BAD_DT;                                                              \
+        return launch(cascade_step_kernel<S, T>, n, stream, x, pid_state, wp_idx, type, params, n_types, pid_cfg, consts, \
+                      wps, n_wp, n, S(dt), n_steps, surf_out, reached_total);                                \
     }
 #define FD_DEFINE_AGENT(NAME, S, T)                                                                          \
     int NAME(int level, S* x, float* pid_state, const uint8_t* type, const double* params, int n_types,      \
@@ -1368,11 +1413,9 @@ int fdyn_pid_compute_batch(const float* cfg, int cfg_per_lane, float* state, con
         FD_CHECK_COMMON(n, n_types)                                                                          \
         if (level < FD_LEVEL_WAYPOINT || level > FD_LEVEL_RATE || n_steps < 0) return FDYN_ERR_BAD_SIZE;     \
         if (n > 0 && (!x || !pid_state || !pid_cfg || !consts || !cmd)) return FDYN_ERR_NULL;                \
-        if (!(dt > 1e-6) || dt > 1.0) return FDYN_ERR_BAD_DT;                                                \
-        hipLaunchKernelGGL((agent_step_kernel<S, T>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           level, x, pid_state, type, params, n_types, pid_cfg, consts, cmd, n, S(dt), n_steps, \
-                           surf_out, cfg_per_lane);                                                     \
-        return launch_status();                                                                              \
+        if (bad_dt(dt)) return FDYN_ERR_BAD_DT;                                                              \
+        return launch(agent_step_kernel<S, T>, n, stream, level, x, pid_state, type, params, n_types, pid_cfg, consts, cmd, \
+                      n, S(dt), n_steps, surf_out, cfg_per_lane);                                            \
     }
 FD_DEFINE_AGENT(fdyn_agent_step_f64, double, double)
 FD_DEFINE_AGENT(fdyn_agent_step_mixed, double, float)
@@ -1392,12 +1435,10 @@ FD_DEFINE_AGENT(fdyn_agent_step_f32, float, float)
         if (!x || !pid_state || !params || !pid_cfg || !consts || !prev_action || !obs_out || !surf_out)     \
             return FDYN_ERR_NULL;                                                                            \
         if (wps ? !wp_idx : !cmd) return FDYN_ERR_NULL;                                                      \
-        if (!(dt > 1e-6) || dt > 1.0) return FDYN_ERR_BAD_DT;                                                \
-        hipLaunchKernelGGL((hybrid_step_kernel<S, T>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           level, x, pid_state, wp_idx, type, params, n_types, pid_cfg, consts, cmd, wps, n_wp, \
-                           actions, learned, throttle_src, prev_action, obs_out, rate_cmd_out, surf_out,     \
-                           reached_total, n, S(dt));                                                         \
-        return launch_status();                                                                              \
+        if (bad_dt(dt)) return FDYN_ERR_BAD_DT;                                                              \
+        return launch(hybrid_step_kernel<S, T>, n, stream, level, x, pid_state, wp_idx, type, params, n_types, pid_cfg, \
+                      consts, cmd, wps, n_wp, actions, learned, throttle_src, prev_action, obs_out, rate_cmd_out, surf_out, \
+                      reached_total, n, S(dt));                                                              \
     }
 FD_DEFINE_HYBRID(fdyn_hybrid_step_f64, double, double)
 FD_DEFINE_HYBRID(fdyn_hybrid_step_mixed, double, float)
@@ -1408,103 +1449,19 @@ FD_DEFINE_CASCADE(fdyn_cascade_step_mixed, double, float)
 FD_DEFINE_CASCADE(fdyn_cascade_step_f32, float, float)
 
 #define FD_DEFINE_ENV(SUFFIX, S, E, T)                                                                       \
-    int fdyn_rate_env_reset_##SUFFIX(S* x, E* e, int32_t* ei, float* pid_state, const uint8_t* mask,         \
-                                     const double* env_consts, const double* pool, int pool_depth,           \
-                                     uint64_t seed, float* obs_out, int64_t n, void* stream)                 \
-    {                                                                                                        \
-        FD_CHECK_COMMON(n, 1)                                                                                \
-        if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;                                                \
-        hipLaunchKernelGGL((rate_env_reset_kernel<S, E>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, e, ei, pid_state, mask, env_consts, pool, pool_depth, seed, obs_out, n); \
-        return launch_status();                                                                              \
-    }                                                                                                        \
-    int fdyn_rate_env_step_##SUFFIX(S* x, E* e, int32_t* ei, const uint8_t* type, const double* params,      \
-                                    int n_types, const double* env_consts, const float* actions,             \
-                                    float* pid_state, const float* pid_cfg, const double* casc_consts,       \
-                                    float* actions_out, const S* rw_delta, const double* pool, int pool_depth, \
-                                    uint64_t seed, int auto_reset, float residual_scale, float* obs_out,     \
-                                    float* reward_f32,                                                       \
-                                    S* reward_full, uint8_t* terminated, uint8_t* truncated,                 \
-                                    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int,              \
-                                    float* ev_flt, int ev_cap, int64_t n, void* stream)                      \
-    {                                                                                                        \
-        FD_CHECK_COMMON(n, n_types)                                                                          \
-        if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;                                                \
-        if ((!actions || residual_scale > 0.0f) && !(pid_state && pid_cfg && casc_consts)) return FDYN_ERR_NULL; \
-        if (!obs_out || !terminated || !truncated || !env_consts) return FDYN_ERR_NULL;                      \
-        if (ev_count && (!ev_int || !ev_flt)) return FDYN_ERR_NULL;                                          \
-        /* records go to FD_EV_SHARDS equal segments: a capacity that is not a positive multiple would give   \
-           segments of zero (or fewer than stated) records and drop episode ends silently */                  \
-        if (ev_count && (ev_cap < FD_EV_SHARDS || ev_cap % FD_EV_SHARDS != 0)) return FDYN_ERR_BAD_SIZE;       \
-        if (sizeof(T) == 4 && n > int64_t(simd_count()) * FD_WAVE)   /* more than one wave per SIMD */            \
-            hipLaunchKernelGGL((rate_env_step_kernel<S, T, true>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg,         \
-                           casc_consts, actions_out, rw_delta, pool, pool_depth, seed, auto_reset,           \
-                           residual_scale, obs_out,                                                          \
-                           reward_f32, reward_full, terminated, truncated, ev_count, ev_count_next, ev_int, ev_flt,  \
-                           ev_cap, n);                                                                  \
-        else                                                                                                 \
-            hipLaunchKernelGGL((rate_env_step_kernel<S, T, false>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg,         \
-                           casc_consts, actions_out, rw_delta, pool, pool_depth, seed, auto_reset,           \
-                           residual_scale, obs_out,                                                          \
-                           reward_f32, reward_full, terminated, truncated, ev_count, ev_count_next, ev_int, ev_flt,  \
-                           ev_cap, n);                                                                  \
-        return launch_status();                                                                              \
-    }
+    int fdyn_rate_env_reset_##SUFFIX(FD_ENV_RESET_PARAMS(S, E), void* stream)                                \
+    { return env_reset<S, E>(FD_ENV_RESET_ARGS, stream); }                                                   \
+    int fdyn_rate_env_step_##SUFFIX(FD_ENV_STEP_PARAMS(S, E), void* stream)                                  \
+    { return env_step<S, E, T>(FD_ENV_STEP_ARGS, stream); }
 FD_DEFINE_ENV(f64, double, double, double)
 FD_DEFINE_ENV(mixed, double, float, float)
 FD_DEFINE_ENV(f32, float, float, float)
 
-// the same two entry points with domain randomisation: + dr [FD_NDR][n] (state dtype), dr_consts [FD_NDC] fp64
 #define FD_DEFINE_ENV_DR(SUFFIX, S, E, T)                                                                    \
-    int fdyn_rate_env_reset_dr_##SUFFIX(S* x, E* e, int32_t* ei, float* pid_state, const uint8_t* mask,      \
-                                        const double* env_consts, const double* pool, int pool_depth,        \
-                                        uint64_t seed, float* obs_out, int64_t n, S* dr, const double* dr_consts, \
-                                        void* stream)                                                        \
-    {                                                                                                        \
-        if (!dr || !dr_consts) return FDYN_ERR_NULL;                                                         \
-        FD_CHECK_COMMON(n, 1)                                                                                \
-        if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;                                                \
-        hipLaunchKernelGGL((rate_env_reset_kernel<S, E, S*, const double*>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, e, ei, pid_state, mask, env_consts, pool, pool_depth, seed, obs_out, n, dr, dr_consts); \
-        return launch_status();                                                                              \
-    }                                                                                                        \
-    int fdyn_rate_env_step_dr_##SUFFIX(S* x, E* e, int32_t* ei, const uint8_t* type, const double* params,   \
-                                       int n_types, const double* env_consts, const float* actions,          \
-                                       float* pid_state, const float* pid_cfg, const double* casc_consts,    \
-                                       float* actions_out, const S* rw_delta, const double* pool, int pool_depth, \
-                                       uint64_t seed, int auto_reset, float residual_scale, float* obs_out,  \
-                                       float* reward_f32,                                                    \
-                                       S* reward_full, uint8_t* terminated, uint8_t* truncated,              \
-                                       int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int,           \
-                                       float* ev_flt, int ev_cap, int64_t n, S* dr, const double* dr_consts, \
-                                       void* stream)                                                         \
-    {                                                                                                        \
-        if (!dr || !dr_consts) return FDYN_ERR_NULL;                                                         \
-        FD_CHECK_COMMON(n, n_types)                                                                          \
-        if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;                                                \
-        if ((!actions || residual_scale > 0.0f) && !(pid_state && pid_cfg && casc_consts)) return FDYN_ERR_NULL; \
-        if (!obs_out || !terminated || !truncated || !env_consts) return FDYN_ERR_NULL;                      \
-        if (ev_count && (!ev_int || !ev_flt)) return FDYN_ERR_NULL;                                          \
-        if (ev_count && (ev_cap < FD_EV_SHARDS || ev_cap % FD_EV_SHARDS != 0)) return FDYN_ERR_BAD_SIZE;       \
-        /* (the f64 build is never register-capped: no fp64 OCC2 instantiation of the randomised kernel) */        \
-        if (sizeof(T) == 4 && n > int64_t(simd_count()) * FD_WAVE)   /* more than one wave per SIMD */            \
-            hipLaunchKernelGGL((rate_env_step_kernel<S, T, (sizeof(T) == 4), S*, const double*>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg,         \
-                           casc_consts, actions_out, rw_delta, pool, pool_depth, seed, auto_reset,           \
-                           residual_scale, obs_out,                                                          \
-                           reward_f32, reward_full, terminated, truncated, ev_count, ev_count_next, ev_int, ev_flt,  \
-                           ev_cap, n, dr, dr_consts);                                                   \
-        else                                                                                                 \
-            hipLaunchKernelGGL((rate_env_step_kernel<S, T, false, S*, const double*>), dim3(grid_for(n)), dim3(FD_BLOCK), 0, (hipStream_t)stream, \
-                           x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg,         \
-                           casc_consts, actions_out, rw_delta, pool, pool_depth, seed, auto_reset,           \
-                           residual_scale, obs_out,                                                          \
-                           reward_f32, reward_full, terminated, truncated, ev_count, ev_count_next, ev_int, ev_flt,  \
-                           ev_cap, n, dr, dr_consts);                                                   \
-        return launch_status();                                                                              \
-    }
+    int fdyn_rate_env_reset_dr_##SUFFIX(FD_ENV_RESET_PARAMS(S, E), S* dr, const double* dr_consts, void* stream) \
+    { return env_reset<S, E>(FD_ENV_RESET_ARGS, stream, dr, dr_consts); }                                    \
+    int fdyn_rate_env_step_dr_##SUFFIX(FD_ENV_STEP_PARAMS(S, E), S* dr, const double* dr_consts, void* stream) \
+    { return env_step<S, E, T>(FD_ENV_STEP_ARGS, stream, dr, dr_consts); }
 FD_DEFINE_ENV_DR(f64, double, double, double)
 FD_DEFINE_ENV_DR(mixed, double, float, float)
 FD_DEFINE_ENV_DR(f32, float, float, float)

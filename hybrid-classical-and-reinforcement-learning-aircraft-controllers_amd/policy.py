@@ -76,6 +76,16 @@ def _run_seq(seq, x):
 
 # k order inside every block of 16 of a layer whose input arrives as the previous layer's MFMA output tile (csrc/policy_fe64.hip)
 _KPERM16 = (0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15)
+_KPERM_CACHE = {}
+
+
+def _kperm(K, device):
+    """Column order of a K-wide weight matrix whose input arrives as MFMA output fragments; one device tensor per (K, device),
+    built once (prepare_inference runs before every rollout: a torch.tensor(list, device=cuda) there is a synchronous H2D copy)."""
+    key = (int(K), str(device))
+    if key not in _KPERM_CACHE:
+        _KPERM_CACHE[key] = torch.tensor([16 * (k // 16) + _KPERM16[k % 16] for k in range(K)], device=device)
+    return _KPERM_CACHE[key]
 
 
 FE_GATE_SCALE = (-1.4426950408889634, 1.0, -2.0 * 1.4426950408889634, -1.4426950408889634)     # gates i, f (unused), g, o
@@ -114,67 +124,6 @@ def pack_fe_weights(w_emb, w1, w2, w_proj):
     wq = w_proj.detach().float()[:, perm(w_proj.shape[1])]
     for s in range(w_proj.shape[0] // 32):
         parts.append(chunk(wq[32 * s:32 * s + 32]))
-    return torch.cat(parts).contiguous()
-
-
-# ---- csrc/policy_rc64.hip: both recurrent cells in one launch, lane = batch row ---------------------------------------------
-# The kernel keeps activations and state in its own layouts (whole 1 KB wave accesses, a lane touches only its own row).  Row
-# 64 wb + 32 t + r lives in lane r + 32 hf of wave-block wb, tile t; hidden unit n = 32 sl + 16 hq + 8 p2 + 4 hf + p01.
-_KPERM_CACHE = {}
-
-
-def _kperm(K, device):
-    """Column order of a K-wide weight matrix whose input arrives as MFMA output fragments; one device tensor per (K, device),
-    built once (prepare_inference runs before every rollout: a torch.tensor(list, device=cuda) there is a synchronous H2D copy)."""
-    key = (int(K), str(device))
-    if key not in _KPERM_CACHE:
-        _KPERM_CACHE[key] = torch.tensor([16 * (k // 16) + _KPERM16[k % 16] for k in range(K)], device=device)
-    return _KPERM_CACHE[key]
-
-
-def rc_pack_x(x):
-    """[B][16 S] row-major activations -> B fragments [B/64][2][S][64][8] bf16 (S k-steps; features 128: S = 8, h 256: S = 16),
-    returned with the row-major shape."""
-    B, K = x.shape
-    return (x.to(torch.bfloat16).reshape(B // 64, 2, 32, K // 32, 2, 2, 2, 4).permute(0, 1, 3, 4, 6, 2, 5, 7)
-            .contiguous().view(B, K))
-
-
-def rc_unpack_x(xi):
-    B, K = xi.shape
-    return xi.reshape(B // 64, 2, K // 32, 2, 2, 32, 2, 4).permute(0, 1, 5, 2, 3, 6, 4, 7).contiguous().view(B, K)
-
-
-rc_pack_h, rc_unpack_h = rc_pack_x, rc_unpack_x
-
-
-def rc_pack_c(c):
-    """[B][256] fp32 cell state -> [B/64][slice 8][tile 2][group 4][lane 64][4] fp32."""
-    B, Hh = c.shape
-    return c.float().reshape(B // 64, 2, 32, Hh // 32, 4, 2, 4).permute(0, 3, 1, 4, 5, 2, 6).contiguous().view(B, Hh)
-
-
-def rc_unpack_c(ci):
-    B, Hh = ci.shape
-    return ci.reshape(B // 64, Hh // 32, 2, 4, 2, 32, 4).permute(0, 2, 5, 1, 3, 4, 6).contiguous().view(B, Hh)
-
-
-def pack_rc_weights(cells):
-    """[(W_ih [4H][128], W_hh [4H][256])] for the actor and the critic -> the byte image csrc/policy_rc64.hip streams through
-    LDS: per cell and 32-unit slice the rows of gates i, g, f, o (the order the kernel multiplies them in), each row
-    [W_ih | W_hh] with the k order of the activation fragments (_KPERM16) + 16 bytes of padding, each 32-row chunk padded to
-    28 KB (seven 1 KB pieces per wave)."""
-    bf = torch.bfloat16
-    parts = []
-    for w_ih, w_hh in cells:
-        dev = w_ih.device
-        w = torch.cat([w_ih.detach().float()[:, _kperm(w_ih.shape[1], dev)], w_hh.detach().float()[:, _kperm(w_hh.shape[1], dev)]], 1)
-        Hh = w.shape[0] // 4
-        for sl in range(Hh // 32):
-            for gate in (0, 2, 1, 3):
-                rows = w[gate * Hh + 32 * sl:gate * Hh + 32 * sl + 32].to(bf)
-                img = torch.cat([rows, torch.zeros(32, 8, dtype=bf, device=dev)], 1).reshape(-1)
-                parts.append(torch.cat([img, torch.zeros(28 * 512 - img.numel(), dtype=bf, device=dev)]))
     return torch.cat(parts).contiguous()
 
 
