@@ -22,6 +22,8 @@ _ENV_STEP = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _u64, _
              _i, _i64, _p]
 _ENV_RESET_DR = _ENV_RESET[:-1] + [_p, _p, _p]               # + dr, dr_consts before the stream
 _ENV_STEP_DR = _ENV_STEP[:-1] + [_p, _p, _p]
+_ENV_STEP_IMG = _ENV_STEP[:-1] + [_p, _p]                   # + the prepared launch image before the stream
+_ENV_STEP_DR_IMG = _ENV_STEP_DR[:-1] + [_p, _p]
 
 SIGNATURES = {
     "fdyn_abi_version": (_i, []),
@@ -40,6 +42,11 @@ SIGNATURES = {
     "fdyn_rate_env_reset_dr_f32": (_i, _ENV_RESET_DR),
     "fdyn_rate_env_step_dr_f64": (_i, _ENV_STEP_DR), "fdyn_rate_env_step_dr_mixed": (_i, _ENV_STEP_DR),
     "fdyn_rate_env_step_dr_f32": (_i, _ENV_STEP_DR),
+    "fdyn_rate_env_image": (_i, [_p, _i, _p, _i, _p, _p]),
+    "fdyn_rate_env_step_img_f64": (_i, _ENV_STEP_IMG), "fdyn_rate_env_step_img_mixed": (_i, _ENV_STEP_IMG),
+    "fdyn_rate_env_step_img_f32": (_i, _ENV_STEP_IMG),
+    "fdyn_rate_env_step_dr_img_f64": (_i, _ENV_STEP_DR_IMG), "fdyn_rate_env_step_dr_img_mixed": (_i, _ENV_STEP_DR_IMG),
+    "fdyn_rate_env_step_dr_img_f32": (_i, _ENV_STEP_DR_IMG),
     "fdyn_lstm_cell_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
     "fdyn_lstm_cell_bwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
     "fdyn_lstm_seq_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i, _p]),

@@ -80,6 +80,24 @@ __device__ __forceinline__ void stage_params_finish(double* s_params, const Stag
     }
 }
 
+// A PREPARED parameter block (the rate env's launch image, fdyn_rate_env_image): [n_types][FD_NP_STAGED] words with the derived
+// ones already in place, so staging is a plain copy -- the same two halves around the caller's per-aircraft loads.
+__device__ __forceinline__ StagedParamWords stage_image_early(const double* __restrict__ staged, int n_types)
+{
+    StagedParamWords w;                                           // FD_MAX_TYPES * FD_NP_STAGED <= 2 * FD_BLOCK
+    const int i0 = threadIdx.x, i1 = FD_BLOCK + threadIdx.x;
+    w.v0 = i0 < n_types * FD_NP_STAGED ? staged[i0] : 0.0;
+    w.v1 = i1 < n_types * FD_NP_STAGED ? staged[i1] : 0.0;
+    w.d = 1.0;
+    return w;
+}
+__device__ __forceinline__ void stage_image_finish(double* s_params, const StagedParamWords& w, int n_types)
+{
+    const int i0 = threadIdx.x, i1 = FD_BLOCK + threadIdx.x;
+    if (i0 < n_types * FD_NP_STAGED) s_params[i0] = w.v0;
+    if (i1 < n_types * FD_NP_STAGED) s_params[i1] = w.v1;
+}
+
 // Cascade constants -> LDS in the glue type, plus the two derived reciprocals the fp32 guidance uses
 template <typename G>
 __device__ __forceinline__ void stage_cascade_consts(G* s_consts, const double* __restrict__ consts)
@@ -719,14 +737,23 @@ __device__ __forceinline__ void env_apply_reset(const G (&rec)[FD_NR], int cmd_t
     e.settle_timer = E(0); e.is_settled = E(0); e.time = E(0); e.ep_return = E(0);
 }
 
-template <typename G>
+// PREP: EC is the env-constant section of a launch image (FD_EC_* words followed by the derived FD_ECD_* ones,
+// fdyn_rate_env_image): the two derived counts are read, not recomputed by every wave of every launch.
+template <typename G, bool PREP = false>
 __device__ __forceinline__ void load_env_consts(const double* __restrict__ EC, EnvConsts<G>& ec)
 {
     ec.dt = G(EC[FD_EC_DT]);
-    ec.max_steps = int(EC[FD_EC_MAX_STEPS]);
-    ec.cmd_type = int(EC[FD_EC_CMD_TYPE]);
+    if constexpr (!PREP) {
+        ec.max_steps = int(EC[FD_EC_MAX_STEPS]);
+        ec.cmd_type = int(EC[FD_EC_CMD_TYPE]);
+    }
     ec.scale = G(EC[FD_EC_DIFFICULTY_SCALE]);
     ec.mr0 = G(EC[FD_EC_MAX_RATE_P]); ec.mr1 = G(EC[FD_EC_MAX_RATE_Q]); ec.mr2 = G(EC[FD_EC_MAX_RATE_R]);
+    if constexpr (PREP) {
+        const int32_t* __restrict__ ic = reinterpret_cast<const int32_t*>(EC + FD_ECD_INTS);
+        ec.max_steps = ic[0]; ec.cmd_type = ic[1]; ec.n_sub = ic[2]; ec.settle_steps = ic[3];
+        return;
+    }
     const double r = EC[FD_EC_DT] / EC[FD_EC_DT_PHYSICS];                       // simulation_backend.py:95
     const long ns = long(r);
     ec.n_sub = ns < 1 ? 1 : int(ns);
@@ -747,6 +774,10 @@ __device__ __forceinline__ void fetch_reset_record(const double* __restrict__ po
         const double* r = pool + (i * pool_depth + (episode % pool_depth)) * FD_NR;
 #pragma unroll
         for (int k = 0; k < FD_NR; ++k) rec[k] = G(r[k]);
+        // the record is complete when this branch ends: with a load still in flight at the join with the drawn record's path,
+        // every later reader of rec[] waits for ALL outstanding memory operations, whichever path the wave took
+#pragma unroll
+        for (int k = 0; k < FD_NR; ++k) asm volatile("" : "+v"(rec[k]));
     } else {
         device_reset_record<G>(seed, uint32_t(i), uint32_t(episode), ec, rec);
     }
@@ -949,7 +980,9 @@ extern "C" int fdyn_debug_read_counts(unsigned* out, int count, int clear)
 // (1 Mi envs: 1.16e9 -> 1.56e9 env-steps/s).  The launcher picks by batch size; the arithmetic is the same.
 // DR = true: the _dr entry points -- wind + gust in the aerodynamics, per-env parameter scales, the gust update and the
 // randomising resets (DESIGN.md "Domain randomisation").  DR = false is the plain env and compiles to its former instructions.
-template <typename S, typename T, bool OCC2, typename... DRA>
+// PREP = true: the _img entry points -- `params` is the staged block section of a prepared launch image ([n_types][FD_NP_STAGED],
+// derived words included) and `EC` its env-constant section; the kernel copies and reads, it derives nothing.
+template <typename S, typename T, bool OCC2, bool PREP, typename... DRA>
 __global__ void __launch_bounds__(FD_BLOCK, OCC2 ? 2 : 1)
 rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict__ es, int32_t* __restrict__ eis,
                      const uint8_t* __restrict__ type, const double* __restrict__ params, int n_types,
@@ -979,7 +1012,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
     const int lane = lm.lane, wave = threadIdx.x / FD_WAVE;
     const bool active = lm.on;
     EnvConsts<S> ec;
-    load_env_consts<S>(EC, ec);
+    load_env_consts<S, PREP>(EC, ec);
     const bool uses_sched = ec.cmd_type == FD_CMD_RAMP || ec.cmd_type == FD_CMD_SINE;
     // actions == null: the fused rate-PID demonstrator drives the env.  residual_scale > 0 (with actions AND pid state):
     // ResidualRateControlEnv -- action = clip(PID + scale * residual) (residual_rate_env.py:99-157).
@@ -1011,7 +1044,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
     // never accessed, but a scratch set-up per launch -- and that build is the parity reference, not the benched one)
     constexpr bool EARLY_PARAMS = sizeof(T) == 4;
     StagedParamWords spw = { 0.0, 0.0, 1.0 };
-    if constexpr (EARLY_PARAMS) spw = stage_params_early(params, n_types);
+    if constexpr (EARLY_PARAMS) spw = PREP ? stage_image_early(params, n_types) : stage_params_early(params, n_types);
     if (active) {
         episode = eis[FD_EI_EPISODE * n + i];
 #pragma unroll
@@ -1030,7 +1063,10 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
             for (int k = 0; k < 5; ++k) dsc[k] = dr[(FD_DR_MASS_S + k) * n + i];
         }
     }
-    if constexpr (EARLY_PARAMS) stage_params_finish<true>(s_params, spw, n_types);
+    if constexpr (PREP) {
+        if constexpr (EARLY_PARAMS) stage_image_finish(s_params, spw, n_types);
+        else stage(s_params, params, n_types * FD_NP_STAGED);
+    } else if constexpr (EARLY_PARAMS) stage_params_finish<true>(s_params, spw, n_types);
     else stage_params<false>(s_params, params, n_types);
     if (pid_mode) {
         stage(s_pid_cfg, pid_cfg, 3 * FD_NPC);
@@ -1183,8 +1219,9 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
 
     FD_STAMP(3)
     // ---- K4: episode-done compaction -- wave ballot + mbcnt prefix, one atomic per wave ---------------------
-    // The returning atomic is ISSUED here and its result consumed only after the auto-reset below: the reset work of the
-    // finished lanes (Philox draws / pool reads, first observation) covers the atomic's round trip.
+    // The returning atomic is ISSUED here and its result consumed only after the auto-reset and the state stores below (the
+    // fence in front of the broadcast holds the first use there: left alone, the compiler moves the cross-lane read up into the
+    // leader's branch and the wave sits out the whole round trip, behind a full drain of the stores before it).
     const unsigned long long done_mask = __ballot(done);
     const bool compact = done_mask != 0ull && ev_count != nullptr;
     int base = 0, prefix = 0;
@@ -1193,7 +1230,13 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
         const int n_done = __popcll(done_mask);
         prefix = __builtin_amdgcn_mbcnt_hi(uint32_t(done_mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(done_mask), 0u));
         const int leader = __ffsll((long long)done_mask) - 1;
-        if (lane == leader) base = atomicAdd(ev_count + shard, n_done);
+        if (lane == leader) {
+            // one lane is already elected: a counter index the compiler takes for per-lane keeps its own wave-level rewrite of
+            // uniform atomics off this one (it elects a lane again and reads the result back right behind the atomic)
+            int cnt = shard;
+            asm volatile("" : "+v"(cnt));
+            base = atomicAdd(ev_count + cnt, n_done);
+        }
     }
     float o_term[FD_OBS_DIM];                                                     // terminal observation of a finished episode
 #pragma unroll
@@ -1232,19 +1275,23 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
         env_store<E>(e, es, n, i, uses_sched);
         eis[FD_EI_STEP * n + i] = step;
         eis[FD_EI_EPISODE * n + i] = episode;
-    }
-    if (compact) {
-        const int leader = __ffsll((long long)done_mask) - 1;
-        base = __shfl(base, leader, FD_WAVE);
-        const int local = base + prefix;
-        if (done && local < cap_s) {
-            const int slot = shard * cap_s + local;
-            ev_int[slot * FD_EV_NI + FD_EV_ENV] = int32_t(i);
-            ev_int[slot * FD_EV_NI + FD_EV_LENGTH] = len_term;
-            ev_int[slot * FD_EV_NI + FD_EV_TERMINATED] = term ? 1 : 0;
-            ev_flt[slot * FD_EV_NF] = ret_term;
+        // The records, still inside the active lanes' block (a finished lane is an active one, the leader among them): on this
+        // path the stores above are all younger than the atomic, so the wait in front of its result's first use is a counted
+        // one -- at a join with the path of a wave without envs it would be a full drain.
+        if (compact) {
+            asm volatile("" : "+v"(base) : : "memory");                          // first use: not before this point
+            const int leader = __ffsll((long long)done_mask) - 1;
+            base = __shfl(base, leader, FD_WAVE);
+            const int local = base + prefix;
+            if (done && local < cap_s) {
+                const int slot = shard * cap_s + local;
+                ev_int[slot * FD_EV_NI + FD_EV_ENV] = int32_t(i);
+                ev_int[slot * FD_EV_NI + FD_EV_LENGTH] = len_term;
+                ev_int[slot * FD_EV_NI + FD_EV_TERMINATED] = term ? 1 : 0;
+                ev_flt[slot * FD_EV_NF] = ret_term;
 #pragma unroll
-            for (int k = 0; k < FD_OBS_DIM; ++k) ev_flt[slot * FD_EV_NF + 1 + k] = o_term[k];
+                for (int k = 0; k < FD_OBS_DIM; ++k) ev_flt[slot * FD_EV_NF + 1 + k] = o_term[k];
+            }
         }
     }
     FD_STAMP(4)
@@ -1254,6 +1301,35 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     FD_STAMP_REAL(6)
+}
+
+// The rate env's prepared launch image (FD_IMG_*): everything the step kernel derives from the parameter table and the env
+// constants alone, computed ONCE by the device functions the kernel itself uses (so every word is the one it would compute) --
+// the staged parameter blocks with their derived words and the env constants with the sub-step and settle-step counts.  One
+// workgroup.  FAST = the fp32-evaluation variants' derived words (Params::derive_lane_from).
+static_assert(FD_NIMG == FD_IMG_PARAMS + FD_MAX_TYPES * FD_NP_STAGED && FD_ECD_INTS + 2 <= FD_IMG_PARAMS, "fdyn_layout.h: image sections");
+template <bool FAST>
+__global__ void __launch_bounds__(FD_BLOCK)
+rate_env_image_kernel(const double* __restrict__ params, int n_types, const double* __restrict__ EC, double* __restrict__ image)
+{
+    double* blocks = image + FD_IMG_PARAMS;
+    for (int i = threadIdx.x; i < FD_MAX_TYPES * FD_NP_STAGED; i += blockDim.x) {
+        const int t = i / FD_NP_STAGED, k = i - t * FD_NP_STAGED;
+        blocks[i] = (t < n_types && k < FD_NP_USED) ? params[t * FD_NP + k] : 0.0;
+    }
+    for (int k = threadIdx.x; k < FD_IMG_PARAMS; k += blockDim.x) if (k < FD_ECD_INTS || k >= FD_ECD_INTS + 2) image[FD_IMG_EC + k] = k < FD_NEC ? EC[k] : 0.0;
+    __syncthreads();                                               // the derived words below land on the zeros above
+    constexpr int NDL = Params<double>::FD_ND_LANES;
+    if (int(threadIdx.x) < n_types * NDL) {
+        const int t = threadIdx.x / NDL;
+        Params<double>::derive_lane<FAST>(threadIdx.x - t * NDL, params + t * FD_NP, blocks + t * FD_NP_STAGED);
+    }
+    if (threadIdx.x == FD_BLOCK - 1) {
+        EnvConsts<double> ec;
+        load_env_consts<double>(EC, ec);
+        int32_t* ic = reinterpret_cast<int32_t*>(image + FD_IMG_EC + FD_ECD_INTS);
+        ic[0] = ec.max_steps; ic[1] = ec.cmd_type; ic[2] = ec.n_sub; ic[3] = ec.settle_steps;
+    }
 }
 
 // =========================================================================================================
@@ -1311,7 +1387,7 @@ static int env_reset(FD_ENV_RESET_PARAMS(S, E), void* stream, DRA... dra)
     return launch(rate_env_reset_kernel<S, E, DRA...>, n, stream, FD_ENV_RESET_ARGS, dra...);
 }
 
-template <typename S, typename E, typename T, typename... DRA>
+template <typename S, typename E, typename T, bool PREP, typename... DRA>
 static int env_step(FD_ENV_STEP_PARAMS(S, E), void* stream, DRA... dra)
 {
     if ((... || !dra)) return FDYN_ERR_NULL;
@@ -1327,7 +1403,7 @@ static int env_step(FD_ENV_STEP_PARAMS(S, E), void* stream, DRA... dra)
     // never register-capped: its flag is false on both sides, no fp64 OCC2 instantiation)
     constexpr bool FP32 = sizeof(T) == 4;
     const bool occ2 = FP32 && n > int64_t(simd_count()) * FD_WAVE;
-    return launch(occ2 ? rate_env_step_kernel<S, T, FP32, DRA...> : rate_env_step_kernel<S, T, false, DRA...>, n, stream,
+    return launch(occ2 ? rate_env_step_kernel<S, T, FP32, PREP, DRA...> : rate_env_step_kernel<S, T, false, PREP, DRA...>, n, stream,
                   FD_ENV_STEP_ARGS, dra...);
 }
 
@@ -1452,7 +1528,7 @@ FD_DEFINE_CASCADE(fdyn_cascade_step_f32, float, float)
     int fdyn_rate_env_reset_##SUFFIX(FD_ENV_RESET_PARAMS(S, E), void* stream)                                \
     { return env_reset<S, E>(FD_ENV_RESET_ARGS, stream); }                                                   \
     int fdyn_rate_env_step_##SUFFIX(FD_ENV_STEP_PARAMS(S, E), void* stream)                                  \
-    { return env_step<S, E, T>(FD_ENV_STEP_ARGS, stream); }
+    { return env_step<S, E, T, false>(FD_ENV_STEP_ARGS, stream); }
 FD_DEFINE_ENV(f64, double, double, double)
 FD_DEFINE_ENV(mixed, double, float, float)
 FD_DEFINE_ENV(f32, float, float, float)
@@ -1461,9 +1537,36 @@ FD_DEFINE_ENV(f32, float, float, float)
     int fdyn_rate_env_reset_dr_##SUFFIX(FD_ENV_RESET_PARAMS(S, E), S* dr, const double* dr_consts, void* stream) \
     { return env_reset<S, E>(FD_ENV_RESET_ARGS, stream, dr, dr_consts); }                                    \
     int fdyn_rate_env_step_dr_##SUFFIX(FD_ENV_STEP_PARAMS(S, E), S* dr, const double* dr_consts, void* stream) \
-    { return env_step<S, E, T>(FD_ENV_STEP_ARGS, stream, dr, dr_consts); }
+    { return env_step<S, E, T, false>(FD_ENV_STEP_ARGS, stream, dr, dr_consts); }
 FD_DEFINE_ENV_DR(f64, double, double, double)
 FD_DEFINE_ENV_DR(mixed, double, float, float)
 FD_DEFINE_ENV_DR(f32, float, float, float)
+
+// The prepared launch image of the rate env and the step entry points that take it: `params` and `env_consts` of the _img entry
+// points are not read, the kernel gets the image's two sections in their place.
+int fdyn_rate_env_image(const double* params, int n_types, const double* env_consts, int fp32_eval, double* image, void* stream)
+{
+    if (n_types < 1 || n_types > FD_MAX_TYPES) return FDYN_ERR_BAD_TYPES;
+    if (!params || !env_consts || !image) return FDYN_ERR_NULL;
+    return launch(fp32_eval ? rate_env_image_kernel<true> : rate_env_image_kernel<false>, FD_BLOCK, stream, params, n_types,
+                  env_consts, image);
+}
+#define FD_DEFINE_ENV_IMG(SUFFIX, S, E, T)                                                                   \
+    int fdyn_rate_env_step_img_##SUFFIX(FD_ENV_STEP_PARAMS(S, E), const double* image, void* stream)         \
+    {                                                                                                        \
+        if (!image) return FDYN_ERR_NULL;                                                                    \
+        params = image + FD_IMG_PARAMS; env_consts = image + FD_IMG_EC;                                      \
+        return env_step<S, E, T, true>(FD_ENV_STEP_ARGS, stream);                                            \
+    }                                                                                                        \
+    int fdyn_rate_env_step_dr_img_##SUFFIX(FD_ENV_STEP_PARAMS(S, E), S* dr, const double* dr_consts, const double* image, \
+                                           void* stream)                                                     \
+    {                                                                                                        \
+        if (!image) return FDYN_ERR_NULL;                                                                    \
+        params = image + FD_IMG_PARAMS; env_consts = image + FD_IMG_EC;                                      \
+        return env_step<S, E, T, true>(FD_ENV_STEP_ARGS, stream, dr, dr_consts);                             \
+    }
+FD_DEFINE_ENV_IMG(f64, double, double, double)
+FD_DEFINE_ENV_IMG(mixed, double, float, float)
+FD_DEFINE_ENV_IMG(f32, float, float, float)
 
 }  // extern "C"

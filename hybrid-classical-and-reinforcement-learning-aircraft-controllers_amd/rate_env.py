@@ -21,6 +21,39 @@ from .params import param_table
 from .samplers import COMMAND_TYPE, EpisodeStreams, env_consts, presample_reset_pool
 
 
+class LaunchImage:
+    """The step's prepared launch image (include/fdyn.h, fdyn_rate_env_image): what the kernel derives from the parameter table
+    and the env constants alone, computed once on the device instead of by every workgroup of every launch.  It is a COPY of
+    both, so `ensure` fills it again whenever either changed since the last fill -- another tensor (or another n_types) was
+    assigned, or the same tensor was written in place (its version counter moved).  The buffer itself is allocated once: a
+    captured graph keeps reading the same address."""
+
+    def __init__(self, precision, fill):
+        self.fp32_eval = precision != "f64"
+        self._fill = fill                  # (params, n_types, env_consts, fp32_eval, image) -> None; launches the fill
+        self.image = None
+        self._key = None
+        self.fills = 0
+
+    @staticmethod
+    def key(params, n_types, env_consts):
+        return (params.data_ptr(), params._version, int(n_types), env_consts.data_ptr(), env_consts._version)
+
+    def ensure(self, params, n_types, env_consts):
+        k = self.key(params, n_types, env_consts)
+        if k != self._key:
+            if self.image is None:
+                self.image = torch.zeros(L.FD_NIMG, dtype=torch.float64, device=params.device)
+            self._fill(params, n_types, env_consts, self.fp32_eval, self.image)
+            # the fill reads both tensors; only then is the image a copy of THIS state of them
+            self._key = self.key(params, n_types, env_consts)
+            self.fills += 1
+        return self.image
+
+    def invalidate(self):
+        self._key = None
+
+
 class GpuRateVecEnv:
     def __init__(self, num_envs: int, difficulty: str = "medium", episode_length: float = 10.0, dt: float = 0.02,
                  command_type: str = "step", seed: Optional[int] = None, precision: str = "mixed",
@@ -88,7 +121,9 @@ class GpuRateVecEnv:
             self.sensor = ObservationNoise(sensor_noise, n, dev)
             self._done_mask = torch.zeros(n, dtype=torch.uint8, device=dev)
         self._reset_fn = getattr(self.lib, f"fdyn_rate_env_reset_{precision}")
-        self._step_fn = getattr(self.lib, f"fdyn_rate_env_step_{precision}")
+        self._step_fn = getattr(self.lib, f"fdyn_rate_env_step_img_{precision}")
+        self._image = LaunchImage(precision, self._fill_image)
+        self.launch_image()                   # filled here, so that a step captured into a graph does not carry the fill
         self._pending = None
         # optional domain randomisation (wind, gusts, per-env mass / inertia / air density; disturbances.py): None keeps the
         # plain entry points and allocates nothing
@@ -110,10 +145,23 @@ class GpuRateVecEnv:
             self.dr_consts = blk
             self.dr = torch.as_tensor(neutral_rows(self.n), device=self.device).to(self.dtype).contiguous()
             self._reset_fn = getattr(self.lib, f"fdyn_rate_env_reset_dr_{self.precision}")
-            self._step_fn = getattr(self.lib, f"fdyn_rate_env_step_dr_{self.precision}")
+            self._step_fn = getattr(self.lib, f"fdyn_rate_env_step_dr_img_{self.precision}")
         else:
             self.dr_consts.copy_(blk)                # in place: a captured graph keeps reading the same block
         return d
+
+    def _fill_image(self, params, n_types, env_consts, fp32_eval, image):
+        assert params.dtype == torch.float64 and env_consts.dtype == torch.float64
+        assert params.shape == (n_types, L.FD_NP) and env_consts.numel() == L.FD_NEC
+        rc = self.lib.fdyn_rate_env_image(_lib.ptr(params), n_types, _lib.ptr(env_consts), int(fp32_eval), _lib.ptr(image),
+                                          _lib.current_stream())
+        _lib.check(rc, "RateControlEnv launch image")
+
+    def launch_image(self):
+        """The prepared launch image of the current `params` / `env_consts` (filled again if either changed).  `step_device`
+        calls this itself; a caller that changes either tensor between the replays of a captured graph calls it after the
+        change, outside the graph."""
+        return self._image.ensure(self.params, self.n_types, self.env_consts)
 
     def _dr_args(self):
         return () if self.dr is None else (_lib.ptr(self.dr), _lib.ptr(self.dr_consts))
@@ -148,6 +196,7 @@ class GpuRateVecEnv:
         acts_out = self.actions_taken if (actions is None or self.residual_scale > 0.0) else None
         cur, nxt = self._ev_counts[self._ev_slot], self._ev_counts[1 - self._ev_slot]
         self._ev_cur, self._ev_slot = cur, 1 - self._ev_slot
+        image = self.launch_image()
         rc = self._step_fn(_lib.ptr(self.x), _lib.ptr(self.e), _lib.ptr(self.ei), _lib.ptr(self.type_index),
                            _lib.ptr(self.params), self.n_types, _lib.ptr(self.env_consts), _lib.ptr(actions),
                            _lib.ptr(self.pid_state), _lib.ptr(self.pid_cfg), _lib.ptr(self.casc_consts),
@@ -155,7 +204,7 @@ class GpuRateVecEnv:
                            self.seed_value, int(auto_reset), self.residual_scale, _lib.ptr(self.obs), _lib.ptr(self.rewards),
                            _lib.ptr(self.rewards_full), _lib.ptr(self.terminated), _lib.ptr(self.truncated),
                            cur.data_ptr(), nxt.data_ptr(), _lib.ptr(self.ev_int), _lib.ptr(self.ev_flt), self.ev_cap,
-                           self.n, *self._dr_args(), _lib.current_stream())
+                           self.n, *self._dr_args(), _lib.ptr(image), _lib.current_stream())
         _lib.check(rc, "RateControlEnv.step")
         if self.sensor is not None:
             mask = None

@@ -232,6 +232,53 @@ int fdyn_rate_env_step_dr_f32(float* x, float* e, int32_t* ei, const uint8_t* ty
                               int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, float* dr,
                               const double* dr_consts, void* stream);
 
+/* ---- rate-control env with a prepared launch image ---------------------------------------------------------------------------
+ * A step derives a few words from the parameter table and env_consts alone: per aircraft type the reciprocals and the sin / cos /
+ * tan of the limits in the staged block (FD_PD_*), and from env_consts the sub-step count and the settle-step count.  The entry
+ * points above compute them in every workgroup of every launch; fdyn_rate_env_image computes them ONCE, with the same device
+ * code, into image [FD_NIMG] fp64 (fdyn_layout.h, FD_IMG_*), and the _img entry points read them from there.  fp32_eval: 1 for
+ * an image the mixed / f32 variants read, 0 for the f64 variant (it reads fewer derived words).  The _img entry points take the
+ * argument list of their plain counterparts plus the image; `params` and `env_consts` are not read (the image holds both) and
+ * may be NULL; n_types is the one the image was filled with.  Results equal the plain entry points' bit for bit.  Fill the image
+ * again whenever params or env_consts change: it is a copy, not a view.                                                      */
+int fdyn_rate_env_image(const double* params, int n_types, const double* env_consts, int fp32_eval, double* image, void* stream);
+int fdyn_rate_env_step_img_f64(double* x, double* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+    const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg, const double* casc_consts,
+    float* actions_out, const double* rw_delta, const double* pool, int pool_depth, uint64_t seed, int auto_reset,
+    float residual_scale, float* obs_out, float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated,
+    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, const double* image,
+    void* stream);
+int fdyn_rate_env_step_dr_img_f64(double* x, double* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+    const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg, const double* casc_consts,
+    float* actions_out, const double* rw_delta, const double* pool, int pool_depth, uint64_t seed, int auto_reset,
+    float residual_scale, float* obs_out, float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated,
+    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, double* dr,
+    const double* dr_consts, const double* image, void* stream);
+int fdyn_rate_env_step_img_mixed(double* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+    const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg, const double* casc_consts,
+    float* actions_out, const double* rw_delta, const double* pool, int pool_depth, uint64_t seed, int auto_reset,
+    float residual_scale, float* obs_out, float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated,
+    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, const double* image,
+    void* stream);
+int fdyn_rate_env_step_dr_img_mixed(double* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+    const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg, const double* casc_consts,
+    float* actions_out, const double* rw_delta, const double* pool, int pool_depth, uint64_t seed, int auto_reset,
+    float residual_scale, float* obs_out, float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated,
+    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, double* dr,
+    const double* dr_consts, const double* image, void* stream);
+int fdyn_rate_env_step_img_f32(float* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+    const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg, const double* casc_consts,
+    float* actions_out, const float* rw_delta, const double* pool, int pool_depth, uint64_t seed, int auto_reset,
+    float residual_scale, float* obs_out, float* reward_f32, float* reward_full, uint8_t* terminated, uint8_t* truncated,
+    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, const double* image,
+    void* stream);
+int fdyn_rate_env_step_dr_img_f32(float* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+    const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg, const double* casc_consts,
+    float* actions_out, const float* rw_delta, const double* pool, int pool_depth, uint64_t seed, int auto_reset,
+    float residual_scale, float* obs_out, float* reward_f32, float* reward_full, uint8_t* terminated, uint8_t* truncated,
+    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, float* dr,
+    const double* dr_consts, const double* image, void* stream);
+
 /* ---- policy-side fused kernels (csrc/policy_kernels.hip) ------------------------------------------------------------
  * LSTM cell point-wise update from pre-activation gates [B][4H] (PyTorch order i,f,g,o; bias already added by the
  * GEMM): replaces the ~40 element-wise launches torch needs per cell (nn.LSTM arithmetic used by

@@ -119,6 +119,17 @@ enum {
     FD_NEC = 8
 };
 
+/* prepared launch image of the rate env (fdyn_rate_env_image, read by fdyn_rate_env_step_img_* / _dr_img_*), fp64 words: what
+ * the step derives from env_consts and the parameter table alone, computed once instead of by every wave of every launch.
+ *   [FD_IMG_EC ..]     the FD_NEC env constants, then the derived counts: RK4 sub-steps per env step (fdyn_num_substeps) and the
+ *                      number of consecutive settled steps at which the settling bonus starts
+ *   [FD_IMG_PARAMS ..] FD_MAX_TYPES staged parameter blocks of FD_NP_STAGED words (FD_P_* then FD_PD_*)                     */
+enum {
+    FD_ECD_INTS = FD_NEC,
+    FD_IMG_EC = 0, FD_IMG_PARAMS = 16,
+    FD_NIMG = FD_IMG_PARAMS + 8 * FD_NP_STAGED
+};
+
 /* one pre-sampled reset record (host NumPy pools in parity mode): 8 IC words + 7 command words        */
 enum {
     FD_R_AIRSPEED = 0, FD_R_ALTITUDE, FD_R_ROLL, FD_R_PITCH, FD_R_YAW, FD_R_P, FD_R_Q, FD_R_R,
