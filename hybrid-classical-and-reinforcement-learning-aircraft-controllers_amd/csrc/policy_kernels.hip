@@ -577,14 +577,18 @@ colsum_mid_kernel(const float* __restrict__ partial, int64_t nb, int N, float* _
     }
 }
 
-// ws[0] += sum adv, ws[1] += sum adv^2
+// ws[0] += sum (adv - adv[0]), ws[1] += sum (adv - adv[0])^2: the moments are taken about a pivot (the first sample, which
+// every lane reads for itself -- no extra launch, no extra state, graph-replay safe).  About zero, the one-pass variance
+// sum a^2 - M mean^2 cancels in fp32 once |mean| >> std (uniformly negative rewards under zero-initialised values early in
+// training; DESIGN.md, PPO update).
 __global__ void __launch_bounds__(256)
 adv_moments_kernel(const float* __restrict__ adv, int64_t M, float* __restrict__ ws)
 {
     __shared__ float s0[256], s1[256];
     float a = 0.0f, b = 0.0f;
+    const float pivot = adv[0];
     for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < M; i += int64_t(gridDim.x) * blockDim.x) {
-        const float v = adv[i];
+        const float v = adv[i] - pivot;
         a += v; b += v * v;
     }
     s0[threadIdx.x] = a; s1[threadIdx.x] = b;
@@ -605,14 +609,15 @@ __global__ void __launch_bounds__(256)
 ppo_loss_kernel(const float* __restrict__ mean /*[M][4]*/, const float* __restrict__ actions /*[M][4]*/,
                 const float* __restrict__ log_std /*[4]*/, const float* __restrict__ values, const float* __restrict__ old_logp,
                 const float* __restrict__ adv, const float* __restrict__ ret, const float* __restrict__ old_values,
-                const float* __restrict__ ws /*[2] adv moments*/, int normalize_adv, float clip_range, float clip_range_vf,
+                const float* __restrict__ ws /*[2] adv moments about adv[0]*/, int normalize_adv, float clip_range, float clip_range_vf,
                 float vf_coef, int64_t M, float* __restrict__ dmean /*[M][4]*/, float* __restrict__ dvalues /*[M]*/,
                 float* __restrict__ stats /*[9]*/)
 {
     __shared__ float red[9][256];
     const float inv_m = 1.0f / float(M);
-    float a_mean = 0.0f, a_scale = 1.0f;
+    float a_pivot = 0.0f, a_mean = 0.0f, a_scale = 1.0f;            // a_mean: of adv - a_pivot (the moments' pivot, adv[0])
     if (normalize_adv) {
+        a_pivot = adv[0];
         a_mean = ws[0] * inv_m;
         const float var = (ws[1] - float(M) * a_mean * a_mean) / float(M > 1 ? M - 1 : 1);      // torch.std: unbiased
         a_scale = 1.0f / (sqrtf(var > 0.0f ? var : 0.0f) + 1e-8f);
@@ -631,7 +636,7 @@ ppo_loss_kernel(const float* __restrict__ mean /*[M][4]*/, const float* __restri
         for (int k = 0; k < 4; ++k) logp += -0.5f * d[k] * d[k] * iv[k] - ls[k] - 0.9189385332046727f;
         const float lr = logp - old_logp[i];
         const float r = __expf(lr);
-        const float A = (adv[i] - a_mean) * a_scale;
+        const float A = ((adv[i] - a_pivot) - a_mean) * a_scale;
         const float rc = fminf(fmaxf(r, 1.0f - clip_range), 1.0f + clip_range);
         const float s1 = A * r, s2 = A * rc;
         const float g_logp = (s1 <= s2) ? -A * r * inv_m : 0.0f;          // d(-min(s1, s2)) / d logp
@@ -940,6 +945,7 @@ int fdyn_ppo_loss(const float* mean, const float* actions, const float* log_std,
     if (!mean || !actions || !log_std || !values || !old_logp || !adv || !ret || !dmean || !dvalues || !stats || !ws ||
         (clip_range_vf > 0.0f && !old_values)) return FDYN_ERR_NULL;
     hipStream_t st = (hipStream_t)stream;
+    if (M < 2) normalize_adv = 0;                                         // SB3 normalises only len(advantages) > 1
     hipLaunchKernelGGL(zero_f32_kernel, dim3(1), dim3(256), 0, st, stats, FDYN_PPO_NSTATS);
     hipLaunchKernelGGL(zero_f32_kernel, dim3(1), dim3(256), 0, st, ws, 2);
     const unsigned nb = unsigned(M / 256 < 1 ? 1 : (M / 256 > 1024 ? 1024 : M / 256));
