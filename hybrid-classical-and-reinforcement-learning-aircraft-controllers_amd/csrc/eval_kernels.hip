@@ -1,4 +1,5 @@
-// eval_kernels.hip -- per-episode rate-control evaluation metrics on the device (gfx950).
+// eval_kernels.hip -- evaluation on the device (gfx950): per-episode rate-control metrics, rewards on recorded sequences and
+// the streamed comparison of two fleets' trajectories (at the end of the file).
 //
 // Reference: learned_controllers/eval/metrics.py:95-362 (MetricsCalculator.compute_metrics and its helpers), fed by
 // the recording loops of learned_controllers/eval_rate.py:70-118,170-233.  The reference walks one Python episode at a
@@ -244,6 +245,176 @@ int launch_reward_seq(const S* errs, const S* actions, const S* prev0, const S* 
     return int(hipGetLastError());
 }
 
+// ---- trajectory comparison, streamed ----------------------------------------------------------------------------------
+// Reference: validation/metrics/trajectory_metrics.py:9-174 (compute_rmse / compute_correlation / compute_max_error and
+// compare_trajectories).  The reference holds both trajectories in DataFrames and reduces them with NumPy / scipy; a fleet
+// cannot be recorded (65 536 aircraft x 6 000 steps x 14 channels is 44 GB), so one lane owns one PAIR of aircraft, keeps the
+// FD_NTA accumulator words of acc [FD_NTA][n] in registers, consumes the launch's T steps in order and writes acc back once:
+// acc traffic is 2 x FD_NTA words per launch whatever T is, every access is a coalesced row read / write along n, and
+// nothing is reduced across lanes -- so feeding a trajectory in chunks of any sizes repeats the same operations in the same
+// order and is bit-identical to one launch.  64-lane workgroups: the 98 carried doubles fill most of the 256 architectural
+// registers of a lane, one wave per SIMD is all a 65 536-pair fleet has anyway (1024 waves on 1024 SIMDs), and small
+// workgroups spread those waves over every CU.  Contraction is off so that differences and products round as NumPy's do.
+constexpr int traj_corr_channel(int j)
+{
+    return j == 0 ? FD_TC_NORTH : j == 1 ? FD_TC_EAST : j == 2 ? FD_TC_DOWN : j == 3 ? FD_TC_ALTITUDE : j == 4 ? FD_TC_ROLL
+         : j == 5 ? FD_TC_PITCH : j == 6 ? FD_TC_YAW : j == 7 ? FD_TC_P : j == 8 ? FD_TC_Q : FD_TC_R;
+}
+constexpr int traj_max_channel(int m)
+{
+    return m == 0 ? FD_TC_NORTH : m == 1 ? FD_TC_EAST : m == 2 ? FD_TC_DOWN : m == 3 ? FD_TC_ROLL : m == 4 ? FD_TC_PITCH : FD_TC_YAW;
+}
+
+// one step of one side: the 14 channels in the reference's units (np.degrees = one multiply by 180 / pi), yaw still wrapped
+template <typename S>
+FD_DEV void traj_channels(const S* __restrict__ x, const S* __restrict__ d, int t, int64_t n, int64_t i, double (&c)[FD_NTC])
+{
+#pragma clang fp contract(off)
+    double xs[FD_NX];
+#pragma unroll
+    for (int w = 0; w < FD_NX; ++w) xs[w] = double(x[(int64_t(t) * FD_NX + w) * n + i]);
+    if (d) {
+        c[FD_TC_AIRSPEED] = double(d[(int64_t(t) * FD_ND + FD_D_AIRSPEED) * n + i]);
+        c[FD_TC_ALTITUDE] = double(d[(int64_t(t) * FD_ND + FD_D_ALTITUDE) * n + i]);
+    } else {
+        const Derived<double> dv = derived<double>(xs);                   // what fdyn_derived_f64 writes
+        c[FD_TC_AIRSPEED] = dv.airspeed;
+        c[FD_TC_ALTITUDE] = dv.altitude;
+    }
+    constexpr double RAD2DEG = 180.0 / 3.141592653589793238462643383279502884;
+    c[FD_TC_NORTH] = xs[FD_X_N]; c[FD_TC_EAST] = xs[FD_X_E]; c[FD_TC_DOWN] = xs[FD_X_D];
+    c[FD_TC_U] = xs[FD_X_U]; c[FD_TC_V] = xs[FD_X_V]; c[FD_TC_W] = xs[FD_X_W];
+    c[FD_TC_ROLL] = xs[FD_X_ROLL] * RAD2DEG; c[FD_TC_PITCH] = xs[FD_X_PITCH] * RAD2DEG; c[FD_TC_YAW] = xs[FD_X_YAW] * RAD2DEG;
+    c[FD_TC_P] = xs[FD_X_P] * RAD2DEG; c[FD_TC_Q] = xs[FD_X_Q] * RAD2DEG; c[FD_TC_R] = xs[FD_X_R] * RAD2DEG;
+}
+
+// np.unwrap(., period=360), one sample: numpy/lib/function_base.py (unwrap) with discont = period / 2
+FD_DEV double traj_unwrap(double cur, double& prev, double& off)
+{
+#pragma clang fp contract(off)
+    const double dd = cur - prev;
+    double m = fmod(dd + 180.0, 360.0);
+    if (m < 0.0) m += 360.0;                                              // np.mod: the result takes the divisor's sign
+    double ddmod = m - 180.0;
+    if (ddmod == -180.0 && dd > 0.0) ddmod = 180.0;
+    double corr = ddmod - dd;
+    if (fabs(dd) < 180.0) corr = 0.0;
+    off += corr;
+    prev = cur;
+    return cur + off;
+}
+
+FD_DEV double traj_correlation(const double (&A)[FD_NTA], int j, double k, unsigned varied)
+{
+#pragma clang fp contract(off)
+    if (k < 2.0) return 0.0;                                              // trajectory_metrics.py:51-52
+    if (((varied >> (2 * j)) & 3u) != 3u) return __builtin_nan("");       // scipy.stats.pearsonr on a constant input
+    const double* w = &A[FD_TA_CORR + j * FD_TA_CORR_WORDS];
+    const double su = w[FD_TA_SU], sv = w[FD_TA_SV];
+    const double cov = w[FD_TA_SUV] - su * sv / k;
+    const double vu = w[FD_TA_SUU] - su * su / k, vv = w[FD_TA_SVV] - sv * sv / k;
+    const double r = cov / (sqrt(vu) * sqrt(vv));
+    return r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);                         // scipy clamps; NaN stays NaN
+}
+
+template <typename SA, typename SB>
+__global__ void __launch_bounds__(64)
+traj_compare_kernel(const SA* __restrict__ xa, const SA* __restrict__ da, const SB* __restrict__ xb, const SB* __restrict__ db,
+                    int T, int64_t n, double* __restrict__ acc /*[FD_NTA][n]*/, double* __restrict__ out /*[FD_NTM][n] or null*/)
+{
+#pragma clang fp contract(off)
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double A[FD_NTA];
+#pragma unroll
+    for (int r = 0; r < FD_NTA; ++r) A[r] = acc[int64_t(r) * n + i];
+    unsigned varied = unsigned(A[FD_TA_VARIED]);
+    for (int t = 0; t < T; ++t) {
+        double a[FD_NTC], b[FD_NTC];
+        traj_channels<SA>(xa, da, t, n, i, a);
+        traj_channels<SB>(xb, db, t, n, i, b);
+        const bool first = A[FD_TA_COUNT] == 0.0;
+        if (first) {
+            A[FD_TA_YAW_PREV_A] = a[FD_TC_YAW]; A[FD_TA_YAW_PREV_B] = b[FD_TC_YAW];
+            A[FD_TA_YAW_OFF_A] = 0.0; A[FD_TA_YAW_OFF_B] = 0.0;
+        }
+        a[FD_TC_YAW] = traj_unwrap(a[FD_TC_YAW], A[FD_TA_YAW_PREV_A], A[FD_TA_YAW_OFF_A]);
+        b[FD_TC_YAW] = traj_unwrap(b[FD_TC_YAW], A[FD_TA_YAW_PREV_B], A[FD_TA_YAW_OFF_B]);
+        double e[FD_NTC];
+#pragma unroll
+        for (int c = 0; c < FD_NTC; ++c) {
+            e[c] = a[c] - b[c];
+            A[FD_TA_SSQ + c] += e[c] * e[c];
+        }
+#pragma unroll
+        for (int m = 0; m < FD_TA_NMAX; ++m) A[FD_TA_MAX + m] = fmax(A[FD_TA_MAX + m], fabs(e[traj_max_channel(m)]));
+        const double pos = sqrt(e[FD_TC_NORTH] * e[FD_TC_NORTH] + e[FD_TC_EAST] * e[FD_TC_EAST] + e[FD_TC_DOWN] * e[FD_TC_DOWN]);
+        A[FD_TA_POS3D_SSQ] += pos * pos;                                  // :108-109: the norm, squared again
+        A[FD_TA_POS3D_MAX] = fmax(A[FD_TA_POS3D_MAX], pos);
+#pragma unroll
+        for (int j = 0; j < FD_TA_NCORR; ++j) {
+            double* w = &A[FD_TA_CORR + j * FD_TA_CORR_WORDS];
+            const double ca = a[traj_corr_channel(j)], cb = b[traj_corr_channel(j)];
+            if (first) { w[FD_TA_PIVOT_A] = ca; w[FD_TA_PIVOT_B] = cb; }
+            const double u = ca - w[FD_TA_PIVOT_A], v = cb - w[FD_TA_PIVOT_B];
+            if (u != 0.0) varied |= 1u << (2 * j);
+            if (v != 0.0) varied |= 2u << (2 * j);
+            w[FD_TA_SU] += u; w[FD_TA_SV] += v;
+            w[FD_TA_SUU] += u * u; w[FD_TA_SVV] += v * v; w[FD_TA_SUV] += u * v;
+        }
+        A[FD_TA_COUNT] += 1.0;
+    }
+    if (T > 0) {
+        A[FD_TA_VARIED] = double(varied);
+#pragma unroll
+        for (int r = 0; r < FD_NTA; ++r) acc[int64_t(r) * n + i] = A[r];
+    }
+    if (!out) return;
+    const double k = A[FD_TA_COUNT];
+    double M[FD_NTM];
+    if (k == 0.0) {
+#pragma unroll
+        for (int r = 0; r < FD_NTM; ++r) M[r] = 0.0;
+    } else {
+        auto rmse = [&](int c) { return sqrt(A[FD_TA_SSQ + c] / k); };
+        double corr[FD_TA_NCORR];
+#pragma unroll
+        for (int j = 0; j < FD_TA_NCORR; ++j) corr[j] = traj_correlation(A, j, k, varied);
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {                                  // north, east, down; roll, pitch, yaw; p, q, r
+            M[FD_TM_POSITION_NORTH_RMSE + 3 * ax] = rmse(FD_TC_NORTH + ax);
+            M[FD_TM_POSITION_NORTH_CORRELATION + 3 * ax] = corr[ax];
+            M[FD_TM_POSITION_NORTH_MAX_ERROR + 3 * ax] = A[FD_TA_MAX + ax];
+            M[FD_TM_ATTITUDE_ROLL_RMSE_DEG + 3 * ax] = rmse(FD_TC_ROLL + ax);
+            M[FD_TM_ATTITUDE_ROLL_CORRELATION + 3 * ax] = corr[4 + ax];
+            M[FD_TM_ATTITUDE_ROLL_MAX_ERROR_DEG + 3 * ax] = A[FD_TA_MAX + 3 + ax];
+            M[FD_TM_RATE_P_RMSE_DPS + 2 * ax] = rmse(FD_TC_P + ax);
+            M[FD_TM_RATE_P_CORRELATION + 2 * ax] = corr[7 + ax];
+            M[FD_TM_VELOCITY_U_RMSE + ax] = rmse(FD_TC_U + ax);
+        }
+        M[FD_TM_POSITION_3D_RMSE] = sqrt(A[FD_TA_POS3D_SSQ] / k);
+        M[FD_TM_POSITION_3D_MAX_ERROR] = A[FD_TA_POS3D_MAX];
+        M[FD_TM_ALTITUDE_RMSE] = rmse(FD_TC_ALTITUDE);
+        M[FD_TM_ALTITUDE_CORRELATION] = corr[3];
+        M[FD_TM_AIRSPEED_RMSE] = rmse(FD_TC_AIRSPEED);
+        M[FD_TM_MEAN_POSITION_CORRELATION] = (corr[0] + corr[1] + corr[2]) / 3.0;        // np.mean: NaN propagates
+        M[FD_TM_MEAN_ATTITUDE_CORRELATION] = (corr[4] + corr[5] + corr[6]) / 3.0;
+        M[FD_TM_OVERALL_CORRELATION] = (M[FD_TM_MEAN_POSITION_CORRELATION] + M[FD_TM_MEAN_ATTITUDE_CORRELATION]) / 2.0;
+    }
+#pragma unroll
+    for (int r = 0; r < FD_NTM; ++r) out[int64_t(r) * n + i] = M[r];
+}
+
+template <typename SA, typename SB>
+int launch_traj_compare(const void* xa, const void* da, const void* xb, const void* db, int T, int64_t n, double* acc,
+                        double* out, void* stream)
+{
+    hipLaunchKernelGGL((traj_compare_kernel<SA, SB>), dim3(unsigned((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                       static_cast<const SA*>(xa), static_cast<const SA*>(da), static_cast<const SB*>(xb),
+                       static_cast<const SB*>(db), T, n, acc, out);
+    return int(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -276,6 +447,18 @@ int fdyn_rate_reward_seq_f32(const float* errs, const float* actions, const floa
                              float* tracking, float* components, float* settle, uint8_t* settled, void* stream)
 {
     return launch_reward_seq<float>(errs, actions, prev0, flight, cmd, params, rstate, dt, T, n, tracking, components, settle, settled, stream);
+}
+
+int fdyn_traj_compare(const void* xa, int a_f32, const void* da, const void* xb, int b_f32, const void* db, int T, int64_t n,
+                      double* acc, double* out, void* stream)
+{
+    if (T < 0 || n < 0) return FDYN_ERR_BAD_SIZE;
+    if (n == 0 || (T == 0 && !out)) return FDYN_OK;
+    if (!acc || (T > 0 && (!xa || !xb))) return FDYN_ERR_NULL;
+    if (a_f32) return b_f32 ? launch_traj_compare<float, float>(xa, da, xb, db, T, n, acc, out, stream)
+                            : launch_traj_compare<float, double>(xa, da, xb, db, T, n, acc, out, stream);
+    return b_f32 ? launch_traj_compare<double, float>(xa, da, xb, db, T, n, acc, out, stream)
+                 : launch_traj_compare<double, double>(xa, da, xb, db, T, n, acc, out, stream);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@
  *   fdyn_rate_metrics_*    MetricsCalculator.compute_metrics learned_controllers/eval/metrics.py:95-362 (fed by eval_rate.py:70-233)
  *   fdyn_rate_reward_seq_* RateTrackingReward.compute / SettlingTimeBonus.compute on recorded sequences (weights as parameters,
  *                          components out)                     learned_controllers/envs/rewards.py:48-137,168-221
+ *   fdyn_traj_compare      compare_trajectories, streamed    validation/metrics/trajectory_metrics.py:9-174
  *   fdyn_sensor_update_*   NoisySensorInterface.update       interfaces/sensor.py:199-243
  *   fdyn_sensor_observe    the same noise model on RateControlEnv observations (rate_env.py:374-408 layout)
  * Policy side (the reference delegates these to torch.nn.LSTM / SB3's PPO, which are not in its tree):
@@ -450,6 +451,21 @@ int fdyn_rate_reward_seq_f64(const double* errs, const double* actions, const do
 int fdyn_rate_reward_seq_f32(const float* errs, const float* actions, const float* prev0, const float* flight,
                              const float* cmd, const double* params, float* rstate, float dt, int T, int64_t n,
                              float* tracking, float* components, float* settle, uint8_t* settled, void* stream);
+
+
+/* ---- trajectory comparison, streamed (csrc/eval_kernels.hip) ----------------------------------------------------------
+ * compare_trajectories (validation/metrics/trajectory_metrics.py:71-174) for n pairs of trajectories at once, with nothing
+ * recorded: the launch consumes T steps of set A and set B in order and carries everything it needs in acc.
+ * xa, xb [T][FD_NX][n] states, fp64 or (a_f32 / b_f32 != 0) fp32 -- with T = 1 a fleet's own x buffer; da, db
+ * [T][FD_ND][n] derived rows in the same type as their side's states (airspeed and altitude are read), NULL = computed
+ * from x as fdyn_derived_f64 does.  acc [FD_NTA][n] fp64 in/out (FD_TA_*; all zeros = a fresh comparison): a later launch
+ * continues exactly where this one stopped, so any chunking of a trajectory gives bit-identical acc and metrics.
+ * out [FD_NTM][n] fp64 (FD_TM_*) or NULL: the metrics finished from acc after the T steps; T = 0 finishes only.
+ * All arithmetic is fp64; attitude and body rates are compared in degrees, yaw unwrapped as np.unwrap(period=360).
+ * A correlation is 0 with fewer than two steps, NaN when either side is constant, and clamped to [-1, 1] otherwise;
+ * no step at all gives zeros everywhere.                                                                                  */
+int fdyn_traj_compare(const void* xa, int a_f32, const void* da, const void* xb, int b_f32, const void* db,
+                      int T, int64_t n, double* acc, double* out, void* stream);
 
 
 /* ---- sensor layer (csrc/sensor_kernels.hip) ---------------------------------------------------------------------------

@@ -185,6 +185,52 @@ enum {
     FD_NM = 17
 };
 
+/* ---- trajectory comparison (fdyn_traj_compare), validation/metrics/trajectory_metrics.py:71-174 --------------------- */
+/* the 14 compared channels: the 12 state words with altitude and airspeed slotted in where the reference's columns have
+ * them; attitude and body rates are compared in degrees (:136-137,150-151), yaw unwrapped (:140-142)                  */
+enum {
+    FD_TC_NORTH = 0, FD_TC_EAST, FD_TC_DOWN, FD_TC_ALTITUDE, FD_TC_U, FD_TC_V, FD_TC_W, FD_TC_AIRSPEED,
+    FD_TC_ROLL, FD_TC_PITCH, FD_TC_YAW, FD_TC_P, FD_TC_Q, FD_TC_R,
+    FD_NTC = 14
+};
+/* the metrics, in the insertion order of the dict compare_trajectories returns (:88-172)                               */
+enum {
+    FD_TM_POSITION_NORTH_RMSE = 0, FD_TM_POSITION_NORTH_CORRELATION, FD_TM_POSITION_NORTH_MAX_ERROR,
+    FD_TM_POSITION_EAST_RMSE, FD_TM_POSITION_EAST_CORRELATION, FD_TM_POSITION_EAST_MAX_ERROR,
+    FD_TM_POSITION_DOWN_RMSE, FD_TM_POSITION_DOWN_CORRELATION, FD_TM_POSITION_DOWN_MAX_ERROR,
+    FD_TM_POSITION_3D_RMSE, FD_TM_POSITION_3D_MAX_ERROR,
+    FD_TM_ALTITUDE_RMSE, FD_TM_ALTITUDE_CORRELATION,
+    FD_TM_VELOCITY_U_RMSE, FD_TM_VELOCITY_V_RMSE, FD_TM_VELOCITY_W_RMSE, FD_TM_AIRSPEED_RMSE,
+    FD_TM_ATTITUDE_ROLL_RMSE_DEG, FD_TM_ATTITUDE_ROLL_CORRELATION, FD_TM_ATTITUDE_ROLL_MAX_ERROR_DEG,
+    FD_TM_ATTITUDE_PITCH_RMSE_DEG, FD_TM_ATTITUDE_PITCH_CORRELATION, FD_TM_ATTITUDE_PITCH_MAX_ERROR_DEG,
+    FD_TM_ATTITUDE_YAW_RMSE_DEG, FD_TM_ATTITUDE_YAW_CORRELATION, FD_TM_ATTITUDE_YAW_MAX_ERROR_DEG,
+    FD_TM_RATE_P_RMSE_DPS, FD_TM_RATE_P_CORRELATION, FD_TM_RATE_Q_RMSE_DPS, FD_TM_RATE_Q_CORRELATION,
+    FD_TM_RATE_R_RMSE_DPS, FD_TM_RATE_R_CORRELATION,
+    FD_TM_MEAN_POSITION_CORRELATION, FD_TM_MEAN_ATTITUDE_CORRELATION, FD_TM_OVERALL_CORRELATION,
+    FD_NTM = 35
+};
+/* carried accumulator rows acc [FD_NTA][n], fp64; all zeros = a fresh comparison:
+ *   COUNT              steps consumed so far (k)
+ *   VARIED             bit 2j (side A) / 2j+1 (side B) set once a sample of correlated channel j differed from the first
+ *                      one -- a side whose bit stays clear is constant, and its correlation is NaN
+ *   YAW_PREV_*, _OFF_* np.unwrap(period=360) streamed: the previous RAW yaw sample (deg) and the running offset per side
+ *   SSQ + c            sum of (a - b)^2 of channel c (FD_TC_*)
+ *   POS3D_SSQ / _MAX   sum and maximum of the per-step 3-D position error
+ *   MAX + m            running max |a - b| of north, east, down, roll, pitch, yaw (m = 0..5)
+ *   CORR + 7 j + ...   correlated channel j (north, east, down, altitude, roll, pitch, yaw, p, q, r): the first sample of
+ *                      each side (the pivots), then the co-moments about them: sum u, sum v, sum u^2, sum v^2, sum u v
+ *                      with u = a - pivot_a, v = b - pivot_b                                                            */
+enum {
+    FD_TA_COUNT = 0, FD_TA_VARIED,
+    FD_TA_YAW_PREV_A, FD_TA_YAW_PREV_B, FD_TA_YAW_OFF_A, FD_TA_YAW_OFF_B,
+    FD_TA_SSQ = 6,
+    FD_TA_POS3D_SSQ = FD_TA_SSQ + FD_NTC, FD_TA_POS3D_MAX,
+    FD_TA_MAX = 22, FD_TA_NMAX = 6,
+    FD_TA_CORR = FD_TA_MAX + FD_TA_NMAX, FD_TA_NCORR = 10,
+    FD_TA_PIVOT_A = 0, FD_TA_PIVOT_B, FD_TA_SU, FD_TA_SV, FD_TA_SUU, FD_TA_SVV, FD_TA_SUV, FD_TA_CORR_WORDS = 7,
+    FD_NTA = FD_TA_CORR + FD_TA_NCORR * FD_TA_CORR_WORDS
+};
+
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
 enum {
