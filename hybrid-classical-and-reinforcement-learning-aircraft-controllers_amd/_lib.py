@@ -82,6 +82,8 @@ SIGNATURES = {
     "fdyn_sensor_observe": (_i, [_p, _p, _p, _p, _p, _u64, _p, _i64, _p]),
     "fdyn_rate_metrics_f32": (_i, [_p, _p, _p, _p, _p, _p, _d, _i, _i, _i64, _p, _p]),
     "fdyn_traj_compare": (_i, [_p, _i, _p, _p, _i, _p, _i, _i64, _p, _p, _p]),
+    "fdyn_trim": (_i, [_p, _p, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p]),
+    "fdyn_linearize": (_i, [_p, _p, _i, _p, _p, _p, _i, _i64, _p, _p, _p]),
 }
 
 _lib = None

@@ -99,6 +99,17 @@ class Simplified6DOF:
         h = self._host
         return AircraftState.from_vector(h[:12].copy(), derived=h[12:16], time=self._time)
 
+    def trim(self, airspeed: float, climb_angle: float = 0.0, turn_rate: float = 0.0, altitude: float = 100.0,
+             heading: float = 0.0, strict: bool = True):
+        """Put the aircraft into steady flight at the given condition (n = 1 of the fleet solver) and hold the trim controls;
+        -> (AircraftState, ControlSurfaces).  The surfaces are the solver's, unclipped; strict raises ValueError when they are
+        not flyable."""
+        res = self._fleet.trim(airspeed, climb_angle, turn_rate, altitude, heading, strict=strict)
+        self._controls = res.surfaces(0)
+        self._time = 0.0
+        self._refresh()
+        return self.get_state(), self._controls
+
 
 class SimulationAircraftBackend(AircraftInterface):
     def __init__(self, config: Optional[dict] = None):
@@ -119,6 +130,12 @@ class SimulationAircraftBackend(AircraftInterface):
         self._physics.reset(initial_state)
         self._state = self._physics.get_state()
         return self._state
+
+    def trim(self, airspeed: float, climb_angle: float = 0.0, turn_rate: float = 0.0, altitude: float = 100.0,
+             heading: float = 0.0, strict: bool = True):
+        """Steady flight at the given condition: -> (AircraftState, ControlSurfaces); the backend is left there, holding them."""
+        self._state, controls = self._physics.trim(airspeed, climb_angle, turn_rate, altitude, heading, strict)
+        return self._state, controls
 
     def get_state(self) -> AircraftState:
         if self._state is None:

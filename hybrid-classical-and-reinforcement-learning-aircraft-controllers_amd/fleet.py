@@ -74,6 +74,28 @@ class BatchedSixDOF:
         """[N][12] float64 host copy."""
         return self.x.to(torch.float64).T.contiguous().cpu().numpy()
 
+    # Steady flight (docs/6dof_mathematical_formulation.tex:1380-1410; the reference codes no solver): hcrl_amd.trim
+    def trim(self, airspeed, climb_angle=0.0, turn_rate=0.0, altitude=100.0, heading=0.0, scales=None, strict: bool = True):
+        """Solve every aircraft's equilibrium at the flight condition (scalars or length-N arrays) in fp64 for its own
+        airframe (and `scales`: per-aircraft multipliers on mass, Ixx, Iyy, Izz, air density), then start the fleet there:
+        `x` and `u` are overwritten in the fleet's storage type and the clock restarts.  Returns the TrimResult.  strict: raise
+        ValueError, BEFORE anything of the fleet is touched, when an aircraft has no flyable equilibrium there."""
+        from . import trim as T
+        spec = torch.as_tensor(T.flight_condition(self.n, airspeed, climb_angle, turn_rate, altitude, heading), device=self.device)
+        res = T.trim_into(spec, self.params, self.type_index, T.scale_rows(self.n, scales, self.device))
+        if strict:
+            T.require_ok(res, f"{type(self).__name__}.trim")
+        self.x.copy_(res.x0)
+        self.u.copy_(res.u0)
+        self.time = 0.0
+        return res
+
+    def linearize(self, scales=None):
+        """(A [12][12][N], B [12][4][N]) float64: d xdot / d x and d xdot / d u of every aircraft at its current `x` and `u`
+        (any state, not only a trim), controls unclipped."""
+        from . import trim as T
+        return T.linearize_into(self.x, self.u, self.params, self.type_index, T.scale_rows(self.n, scales, self.device))
+
 
 class BatchedCascade(BatchedSixDOF):
     """N aircraft each flying the same waypoint mission under the 5-level cascaded PID stack."""

@@ -468,6 +468,31 @@ int fdyn_traj_compare(const void* xa, int a_f32, const void* da, const void* xb,
                       int T, int64_t n, double* acc, double* out, void* stream);
 
 
+/* ---- steady flight and linearisation (csrc/trim_kernels.hip) ----------------------------------------------------------
+ * fdyn_trim: the trim condition of docs/6dof_mathematical_formulation.tex:1380-1410 (x_dot = 0, "set controls to estimated
+ * trim values" -- the reference states it and codes no solver), solved per aircraft.  spec [FD_NTS][n] fp64 (FD_TS_*):
+ * airspeed V, flight-path angle gamma, turn rate psi_dot, altitude h, heading psi0.  type [n] uint8 or NULL (= 0);
+ * scales [FD_NSC][n] fp64 multipliers on mass, Ixx, Iyy, Izz, air density, or NULL (= 1); params [n_types][FD_NP].
+ * Unknowns z = (alpha, theta, phi, elevator, aileron, rudder, throttle), controls normalised as set_controls takes them and
+ * NOT clipped while solving.  State from z: N = E = 0, D = -h, (u, v, w) = (V cos alpha, 0, V sin alpha), attitude
+ * (phi, theta, psi0), (p, q, r) = psi_dot (-sin theta, sin phi cos theta, cos phi cos theta).  Residual
+ * F = (u_dot, v_dot, w_dot, p_dot, q_dot, r_dot, D_dot + V sin gamma).  Newton from z0 = (0.05, 0.05 + gamma,
+ * atan(V psi_dot / g), 0, 0, 0, 0.5): Jacobian by central differences with step 1e-6 (divided by the step actually taken),
+ * full step from a 7 x 7 elimination with partial pivoting, a pivot below 1e-14 max|J| = singular, stop at
+ * max|dz| < 1e-12, at most 20 steps.  Outputs, always the last iterate: x0 [FD_NX][n], u0 [FD_NU][n] fp64,
+ * residual [n] = max|F| there (NaN for a BAD_SPEC lane), iters [n], status [n] int32 (FD_TRIM_* bits, 0 = flyable).     */
+int fdyn_trim(const double* spec, const uint8_t* type, const double* scales, const double* params, int n_types, int64_t n,
+              double* x0, double* u0, double* residual, int32_t* iters, int32_t* status, void* stream);
+/* fdyn_linearize: the "linearised rate dynamics near trim" of docs/control_hierarchy_design.tex:282, which the reference
+ * derives its PID structure from and never computes -- here for the full 12-state model at ANY state.  x [FD_NX][n] and
+ * u [FD_NU][n], both fp64 or (xu_f32 != 0) both fp32; type, scales, params as above.  A [FD_NX * FD_NX][n] with
+ * A[12 i + j] = d xdot_i / d x_j and B [FD_NX * FD_NU][n] with B[4 i + k] = d xdot_i / d u_k, fp64: central differences of
+ * the unclipped equations of motion, state steps 1e-5 max(1, |x_j|), control steps 1e-5, each divided by
+ * (x + s) - (x - s).  32 evaluations per aircraft in one launch.  Neither entry point synchronises or allocates.          */
+int fdyn_linearize(const void* x, const void* u, int xu_f32, const uint8_t* type, const double* scales, const double* params,
+                   int n_types, int64_t n, double* A, double* B, void* stream);
+
+
 /* ---- sensor layer (csrc/sensor_kernels.hip) ---------------------------------------------------------------------------
  * NoisySensorInterface.update (interfaces/sensor.py:199-243) for n aircraft: meas [FD_NMS][n] = the 12 state words +
  * airspeed + altitude with Gaussian noise, body rates additionally offset by the gyro bias; bias [FD_NSB][n]

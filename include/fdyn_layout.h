@@ -231,6 +231,25 @@ enum {
     FD_NTA = FD_TA_CORR + FD_TA_NCORR * FD_TA_CORR_WORDS
 };
 
+/* ---- steady-flight solver and linearisation (fdyn_trim / fdyn_linearize, csrc/trim_kernels.hip) ------------------------ */
+/* flight condition per aircraft, spec [FD_NTS][n] fp64: airspeed (m/s), flight-path angle (rad, positive up), turn rate
+ * (rad/s, positive to the right), altitude (m), heading (rad)                                                          */
+enum { FD_TS_AIRSPEED = 0, FD_TS_CLIMB_ANGLE, FD_TS_TURN_RATE, FD_TS_ALTITUDE, FD_TS_HEADING, FD_NTS = 5 };
+/* per-aircraft multipliers on the type's block, scales [FD_NSC][n] fp64 (the order of FD_DR_MASS_S .. FD_DR_RHO_S)       */
+enum { FD_SC_MASS = 0, FD_SC_IXX, FD_SC_IYY, FD_SC_IZZ, FD_SC_RHO, FD_NSC = 5 };
+/* status bits of a trim; 0 = a flyable equilibrium
+ *   NOT_CONVERGED  the Newton iteration hit a singular Jacobian, a non-finite value or its iteration limit
+ *   CONTROL_RANGE  a surface outside [-1, 1] or the throttle outside [0, 1]: the root needs more authority than there is
+ *   ALPHA_LIMIT    |alpha| >= max_alpha: the aerodynamic alpha is clipped there, the root balances the forces with a frozen
+ *                  lift coefficient and is not a flight condition
+ *   PITCH_LIMIT    |theta| >= max_pitch (the Euler-rate clamp is active)
+ *   BAD_SPEC       a spec word is not finite or the airspeed is not positive: nothing was solved                         */
+enum {
+    FD_TRIM_NOT_CONVERGED = 1, FD_TRIM_CONTROL_RANGE = 2, FD_TRIM_ALPHA_LIMIT = 4, FD_TRIM_PITCH_LIMIT = 8, FD_TRIM_BAD_SPEC = 16
+};
+/* the longitudinal (u, w, q, theta | elevator, throttle) and lateral (v, p, r, phi | aileron, rudder) sub-systems are read
+ * out of A [FD_NX * FD_NX][n] and B [FD_NX * FD_NU][n] on the host (hcrl_amd.trim)                                       */
+
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
 enum {
