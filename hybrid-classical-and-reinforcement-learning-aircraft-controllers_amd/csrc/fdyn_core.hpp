@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/fdyn_layout.h"
+#include "philox.hpp"
 
 namespace fdyn {
 
@@ -1329,6 +1330,6 @@ struct Philox {
         for (int i = 0; i < 4; ++i) out[i] = ctr[i];
     }
 };
-FD_DEV float u01(uint32_t r) { return (float(r >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0,1)
+FD_DEV float u01(uint32_t r) { return ::philox_u01(r); }   // (0,1), philox.hpp
 
 }  // namespace fdyn

@@ -674,10 +674,10 @@ __device__ __forceinline__ void device_reset_record(uint64_t seed, uint32_t env,
 {
     Philox ph;
     uint32_t r0[4], r1[4], r2[4], r3[4];
-    ph.block(seed, env, episode, 0u, 0u, r0);
-    ph.block(seed, env, episode, 0u, 1u, r1);
-    ph.block(seed, env, episode, 0u, 2u, r2);
-    ph.block(seed, env, episode, 0u, 3u, r3);
+    ph.block(seed, env, episode, 0u, FD_PHX_RESET + 0, r0);
+    ph.block(seed, env, episode, 0u, FD_PHX_RESET + 1, r1);
+    ph.block(seed, env, episode, 0u, FD_PHX_RESET + 2, r2);
+    ph.block(seed, env, episode, 0u, FD_PHX_RESET + 3, r3);
     const float d15 = 0.26179938779914943f;     // radians(15)
     rec[FD_R_AIRSPEED] = G(15.0f + 15.0f * u01(r0[0]));
     rec[FD_R_ALTITUDE] = G(50.0f + 150.0f * u01(r0[1]));
@@ -1161,7 +1161,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
                 for (int k = 0; k < 3; ++k) delta[k] = rw_delta[k * n + i];
             } else {                                                              // generators.py:147-164 on device
                 Philox ph; uint32_t r[4];
-                ph.block(seed, uint32_t(i), uint32_t(episode), uint32_t(step), 7u, r);
+                ph.block(seed, uint32_t(i), uint32_t(episode), uint32_t(step), FD_PHX_RANDOM_WALK, r);
                 const float m0 = sqrtf(-2.0f * logf(u01(r[0]))), m1 = sqrtf(-2.0f * logf(u01(r[2])));
                 const float n0 = m0 * cosf(6.283185307f * u01(r[1])), n1 = m0 * sinf(6.283185307f * u01(r[1]));
                 const float n2 = m1 * cosf(6.283185307f * u01(r[3]));

@@ -368,9 +368,9 @@ gaussian_head_kernel(const MT* __restrict__ mean /*[B][4]*/, const float* __rest
     float z[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     if (!deterministic) {
         uint32_t r[4];
-        philox4(seed, uint32_t(i), uint32_t(i >> 32), step_ptr ? *step_ptr : 0u, 0x51u, r);
-        const float u0 = (float(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = (float(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = (float(r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = (float(r[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        philox4(seed, uint32_t(i), uint32_t(i >> 32), step_ptr ? *step_ptr : 0u, FD_PHX_ACTION, r);
+        const float u0 = philox_u01(r[0]), u1 = philox_u01(r[1]);
+        const float u2 = philox_u01(r[2]), u3 = philox_u01(r[3]);
         const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
         z[0] = ra * __cosf(6.283185307f * u1); z[1] = ra * __sinf(6.283185307f * u1);
         z[2] = rb * __cosf(6.283185307f * u3); z[3] = rb * __sinf(6.283185307f * u3);
@@ -421,9 +421,9 @@ policy_heads_kernel(const uint16_t* __restrict__ pi_hidden /*[B][64] bf16*/, con
     float z[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     if (!deterministic) {
         uint32_t r[4];
-        philox4(seed, uint32_t(i), uint32_t(i >> 32), step_ptr ? *step_ptr : 0u, 0x51u, r);
-        const float u0 = (float(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = (float(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = (float(r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = (float(r[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        philox4(seed, uint32_t(i), uint32_t(i >> 32), step_ptr ? *step_ptr : 0u, FD_PHX_ACTION, r);
+        const float u0 = philox_u01(r[0]), u1 = philox_u01(r[1]);
+        const float u2 = philox_u01(r[2]), u3 = philox_u01(r[3]);
         const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
         z[0] = ra * __cosf(6.283185307f * u1); z[1] = ra * __sinf(6.283185307f * u1);
         z[2] = rb * __cosf(6.283185307f * u3); z[3] = rb * __sinf(6.283185307f * u3);

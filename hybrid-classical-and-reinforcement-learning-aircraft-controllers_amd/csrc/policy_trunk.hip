@@ -301,9 +301,9 @@ policy_trunk_kernel(const uint16_t* __restrict__ h_pi, const uint16_t* __restric
                     float z[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
                     if (!hd.deterministic) {                                           // as policy_heads_kernel: same key, same Box-Muller
                         uint32_t rn[4];
-                        philox4(hd.seed, uint32_t(my_row), uint32_t(my_row >> 32), hd.step ? *hd.step : 0u, 0x51u, rn);
-                        const float u0 = (float(rn[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = (float(rn[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-                        const float u2 = (float(rn[2] >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = (float(rn[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+                        philox4(hd.seed, uint32_t(my_row), uint32_t(my_row >> 32), hd.step ? *hd.step : 0u, FD_PHX_ACTION, rn);
+                        const float u0 = philox_u01(rn[0]), u1 = philox_u01(rn[1]);
+                        const float u2 = philox_u01(rn[2]), u3 = philox_u01(rn[3]);
                         const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
                         z[0] = ra * __cosf(6.283185307f * u1); z[1] = ra * __sinf(6.283185307f * u1);
                         z[2] = rb * __cosf(6.283185307f * u3); z[3] = rb * __sinf(6.283185307f * u3);

@@ -28,9 +28,9 @@ __device__ __forceinline__ void draw_normals(uint64_t seed, int64_t i, uint32_t 
 #pragma unroll
     for (int b = 0; b < FD_NSZ / 4; ++b) {
         uint32_t r[4];
-        philox4(seed, uint32_t(i), uint32_t(i >> 32), step, 0x60u + uint32_t(b), r);
-        const float u0 = (float(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = (float(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = (float(r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = (float(r[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        philox4(seed, uint32_t(i), uint32_t(i >> 32), step, FD_PHX_SENSOR + uint32_t(b), r);
+        const float u0 = philox_u01(r[0]), u1 = philox_u01(r[1]);
+        const float u2 = philox_u01(r[2]), u3 = philox_u01(r[3]);
         const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
         z[4 * b + 0] = S(ra * __cosf(6.283185307f * u1)); z[4 * b + 1] = S(ra * __sinf(6.283185307f * u1));
         z[4 * b + 2] = S(rb * __cosf(6.283185307f * u3)); z[4 * b + 3] = S(rb * __sinf(6.283185307f * u3));

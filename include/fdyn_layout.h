@@ -171,9 +171,15 @@ enum {
     FD_DC_REDRAW,
     FD_NDC = 21
 };
-/* Philox counter words (fourth counter word; the first three are env, episode, step) of the randomisation draws -- the IC and
- * command draws use 0..3 and the random-walk command 7                                                                       */
-enum { FD_PHX_DR_RESET = 16, FD_PHX_DR_GUST0 = 19, FD_PHX_GUST = 20 };
+/* Philox counter words: the fourth counter word names the consumer, the key is the 64-bit seed (DESIGN.md "Philox counter
+ * layouts").  Env kernels, counter (env, episode, step, word): the IC and command record FD_PHX_RESET..+3, the random-walk command
+ * increment FD_PHX_RANDOM_WALK, the randomisation rows FD_PHX_DR_RESET..+2, the initial gust FD_PHX_DR_GUST0, the gust update
+ * FD_PHX_GUST.  Row kernels, counter (row low, row high, step, word): the policy's action noise FD_PHX_ACTION, the five blocks of
+ * a sensor update FD_PHX_SENSOR..+4.                                                                                          */
+enum {
+    FD_PHX_RESET = 0, FD_PHX_RANDOM_WALK = 7, FD_PHX_DR_RESET = 16, FD_PHX_DR_GUST0 = 19, FD_PHX_GUST = 20,
+    FD_PHX_ACTION = 0x51, FD_PHX_SENSOR = 0x60
+};
 
 /* ---- per-episode evaluation metrics, learned_controllers/eval/metrics.py:8-40 (field order of RateControlMetrics) */
 enum {
