@@ -17,6 +17,7 @@ _SIXDOF = [_p, _p, _p, _p, _i, _i64, _d, _i, _p, _p]
 _CASCADE = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
 _AGENT = [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]
 _HYBRID = [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i64, _d, _p]
+_LQR_STEP = [_p, _p, _p, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
 _ENV_RESET = [_p, _p, _p, _p, _p, _p, _p, _i, _u64, _p, _i64, _p]
 _ENV_STEP = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _u64, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p,
              _i, _i64, _p]
@@ -84,6 +85,8 @@ SIGNATURES = {
     "fdyn_traj_compare": (_i, [_p, _i, _p, _p, _i, _p, _i, _i64, _p, _p, _p]),
     "fdyn_trim": (_i, [_p, _p, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p]),
     "fdyn_linearize": (_i, [_p, _p, _i, _p, _p, _p, _i, _i64, _p, _p, _p]),
+    "fdyn_lqr_design": (_i, [_p, _p, _p, _i, _i64, _p, _p, _p, _p, _p]),
+    "fdyn_lqr_step_f64": (_i, _LQR_STEP), "fdyn_lqr_step_mixed": (_i, _LQR_STEP), "fdyn_lqr_step_f32": (_i, _LQR_STEP),
 }
 
 _lib = None

@@ -323,3 +323,53 @@ class WaypointAgent(_SingleAgent):
         """waypoint_agent.py:255-267: 3-D distance to the waypoint below the acceptance radius."""
         err = np.array([waypoint.north - state.north, waypoint.east - state.east, waypoint.down - state.down])
         return bool(np.linalg.norm(err) < self.acceptance_radius)
+
+
+class LQRAgent:
+    """State feedback about a trim point for one aircraft, with the reference agents' surface: u = u0 - K (x - x0), clipped
+    as set_controls clips (fdyn_lqr_step_f64 with n_steps = 0, the control law the fleets fly).  `design_or_gains` is an
+    LqrDesign (lane `lane` is taken) or the 16 gains (K_lon 2 x 4 row-major, then K_lat 2 x 4); x0 [12] and u0 [4] are the trim
+    point, taken from the design when it carries one."""
+
+    def __init__(self, design_or_gains, x0=None, u0=None, lane: int = 0):
+        from .lqr import LqrDesign
+        self._fleet = BatchedSixDOF(1, "f64")
+        dev = self._fleet.device
+        col = lambda v, rows: torch.as_tensor(np.array(v, np.float64).reshape(rows, 1), device=dev).contiguous()   # noqa: E731
+        if isinstance(design_or_gains, LqrDesign):
+            d = design_or_gains
+            K = d.K[:, lane:lane + 1].to(dev).contiguous()
+            x0 = d.x0[:, lane].cpu().numpy() if x0 is None else x0
+            u0 = d.u0[:, lane].cpu().numpy() if u0 is None else u0
+        else:
+            K = col(design_or_gains, L.FD_NLQK)
+        if x0 is None or u0 is None:
+            raise ValueError("LQRAgent needs the trim point x0 [12] and u0 [4]")
+        one = lambda dtype: torch.zeros(1, dtype=dtype, device=dev)   # noqa: E731
+        self._design = LqrDesign(K, one(torch.float64), one(torch.int32), one(torch.int32), col(x0, L.FD_NX), col(u0, L.FD_NU))
+
+    def get_control_level(self) -> ControlMode:
+        return ControlMode.SURFACE
+
+    def set_trim(self, x0, u0):
+        """A new point to regulate to (the gains stay: schedule them by designing again)."""
+        d, dev = self._design, self._fleet.device
+        d.x0 = torch.as_tensor(np.array(x0, np.float64).reshape(L.FD_NX, 1), device=dev).contiguous()
+        d.u0 = torch.as_tensor(np.array(u0, np.float64).reshape(L.FD_NU, 1), device=dev).contiguous()
+
+    def compute_action(self, command, state: AircraftState, dt: Optional[float] = None) -> ControlSurfaces:
+        """`command` is ignored (None is fine) unless it is a pair (x0, u0): a new trim point."""
+        if isinstance(command, (tuple, list)) and len(command) == 2:
+            self.set_trim(*command)
+        f = self._fleet
+        f.x.copy_(torch.as_tensor(state.to_vector(), device=f.device).reshape(L.FD_NX, 1))
+        f.step_lqr(self._design, 0, 0.01 if dt is None else dt)
+        s = f.u[:, 0].cpu().numpy()
+        return ControlSurfaces(elevator=float(s[L.FD_U_ELEVATOR]), aileron=float(s[L.FD_U_AILERON]),
+                               rudder=float(s[L.FD_U_RUDDER]), throttle=float(s[L.FD_U_THROTTLE]))
+
+    def reset(self):
+        pass                                 # static feedback: no state to clear
+
+    def __repr__(self) -> str:
+        return "LQRAgent(level=SURFACE)"

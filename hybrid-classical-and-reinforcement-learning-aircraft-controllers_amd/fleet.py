@@ -18,6 +18,8 @@ from .params import AircraftParams, param_table
 
 
 class BatchedSixDOF:
+    _trim = None                 # (TrimResult, scales) of the last .trim(): the point design_lqr designs at
+
     def __init__(self, n: int, precision: str = "f64", types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, device=None):
         self.lib = _lib.load()
@@ -82,12 +84,14 @@ class BatchedSixDOF:
         ValueError, BEFORE anything of the fleet is touched, when an aircraft has no flyable equilibrium there."""
         from . import trim as T
         spec = torch.as_tensor(T.flight_condition(self.n, airspeed, climb_angle, turn_rate, altitude, heading), device=self.device)
-        res = T.trim_into(spec, self.params, self.type_index, T.scale_rows(self.n, scales, self.device))
+        scale_rows = T.scale_rows(self.n, scales, self.device)
+        res = T.trim_into(spec, self.params, self.type_index, scale_rows)
         if strict:
             T.require_ok(res, f"{type(self).__name__}.trim")
         self.x.copy_(res.x0)
         self.u.copy_(res.u0)
         self.time = 0.0
+        self._trim = (res, scale_rows)
         return res
 
     def linearize(self, scales=None):
@@ -95,6 +99,34 @@ class BatchedSixDOF:
         (any state, not only a trim), controls unclipped."""
         from . import trim as T
         return T.linearize_into(self.x, self.u, self.params, self.type_index, T.scale_rows(self.n, scales, self.device))
+
+    # Gain-scheduled LQR (hcrl_amd.lqr): the design step between trim / linearize and flight
+    def design_lqr(self, weights=None, scales=None, strict: bool = True):
+        """An LQR gain for every aircraft at the fleet's current trim (the last `.trim(...)`), each designed on its own
+        linear model: LqrDesign with K [16][N], status 0 = a certified stabilising gain.  weights: None (LqrWeights()), an
+        LqrWeights, or penalties [12] / [12][N]; scales: None = the multipliers the trim was solved with.  strict: raise
+        ValueError when an aircraft has no certified gain.  The fleet's state is not touched."""
+        from . import lqr as Q
+        if self._trim is None:
+            raise ValueError(f"{type(self).__name__}.design_lqr: the fleet has no trim; call .trim(...) first")
+        res, trim_scales = self._trim
+        out = Q.design_lqr(res, self.params, self.type_index, trim_scales if scales is None else scales, weights)
+        if strict:
+            Q.require_ok(out, f"{type(self).__name__}.design_lqr")
+        return out
+
+    def step_lqr(self, design, n_steps: int = 1, dt: Optional[float] = None):
+        """n_steps x {u = u0 - K (x - x0), clipped as set_controls clips -> one RK4 of dt} in ONE launch (dt None: the fleet's
+        own `dt` where it has one, else 0.01 s).  `u` receives the last applied controls; `lqr_saturated_steps` [N] int32
+        counts, per aircraft, the steps in which a control was clipped.  The fleet integrates its airframes' own parameter
+        blocks: a design made with `scales` belongs to an aircraft this fleet does not fly."""
+        from . import lqr as Q
+        if dt is None:
+            dt = getattr(self, "dt", 0.01)
+        if getattr(self, "lqr_saturated_steps", None) is None:
+            self.lqr_saturated_steps = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        Q.step_into(self.precision, self.x, design, self.params, self.type_index, dt, n_steps, self.u, self.lqr_saturated_steps)
+        self.time += dt * n_steps
 
 
 class BatchedCascade(BatchedSixDOF):

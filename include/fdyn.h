@@ -493,6 +493,38 @@ int fdyn_linearize(const void* x, const void* u, int xu_f32, const uint8_t* type
                    int n_types, int64_t n, double* A, double* B, void* stream);
 
 
+/* ---- gain-scheduled LQR (csrc/lqr_kernels.hip) ---------------------------------------------------------------------------
+ * fdyn_lqr_design: the design step between fdyn_linearize and flight, one lane per aircraft, fp64.  A [FD_NX * FD_NX][n] and
+ * B [FD_NX * FD_NU][n] exactly as fdyn_linearize writes them; weights [FD_NLQW] fp64 shared, or (weights_per_lane != 0)
+ * [FD_NLQW][n]: a sweep of weight sets in one launch.  Per block -- longitudinal (u, w, q, theta | elevator, throttle) and
+ * lateral (v, p, r, phi | aileron, rudder), (a, b) cut out of A, B -- the equation a^T X + X a - X G X + Q = 0 with
+ * G = b R^-1 b^T is solved by the structure-preserving doubling algorithm: gamma = max(1, |a|_inf), a_g = a - gamma I,
+ * W = a_g^T + Q a_g^-1 G, A_0 = I + 2 gamma W^-T, G_0 = 2 gamma a_g^-1 G W^-1, H_0 = 2 gamma W^-1 Q a_g^-1; then with
+ * M = (I + G_k H_k)^-1: A_k+1 = A_k M A_k, G_k+1 = G_k + A_k M G_k A_k^T, H_k+1 = H_k + A_k^T H_k M A_k, until
+ * max|H_k+1 - H_k| <= 1e-13 max(1, max|H_k+1|), at most 30 times.  X = (H + H^T) / 2, K = R^-1 b^T X.  Every 4 x 4 inverse
+ * is an elimination with partial pivoting; a pivot below 1e-14 max|matrix| = singular.
+ * Outputs: K [FD_NLQK][n] (FD_LQK_*), residual [n] = max|a^T X + X a - X G X + Q| / max(1, max|X|) of the worse block (NaN for
+ * a BAD_INPUT lane), iters [n] (the larger of the two blocks), status [n] int32 (FD_LQR_* bits).  Status 0 is a certificate:
+ * with Q > 0, X > 0 (an unrolled 4 x 4 L D L^T with every d > 0) and a residual <= 1e-8,
+ * (a - b K)^T X + X (a - b K) = -Q - K^T R K < 0, so X is a Lyapunov function of the closed block and a - b K is Hurwitz --
+ * proved per lane without computing an eigenvalue.  A lane with status != 0 gets K = 0 in all FD_NLQK words: flown, it
+ * holds u0.  The words of A and B outside the two blocks are not read.  Neither entry point synchronises or allocates.   */
+int fdyn_lqr_design(const double* A, const double* B, const double* weights, int weights_per_lane, int64_t n, double* K,
+                    double* residual, int32_t* iters, int32_t* status, void* stream);
+/* fdyn_lqr_step_*: n_steps x { u = u0 - K delta -> set_controls' clip -> one RK4 of dt } in one launch, the physics of
+ * fdyn_agent_step_* to the bit.  delta = the eight words (u, w, q, theta | v, p, r, phi) of x - x0, formed in fp64, the two
+ * angle differences wrapped to [-pi, pi); the feedback runs in fp64 (_f64) or fp32 (_mixed, _f32).  x [FD_NX][n] is updated
+ * in place; x0 [FD_NX][n], u0 [FD_NU][n], K [FD_NLQK][n] fp64; type [n] uint8 or NULL, params [n_types][FD_NP].
+ * surf_out [FD_NU][n] or NULL: the last applied, clipped controls.  sat_steps [n] int32 or NULL: += the number of steps in
+ * which any control was clipped.  n_steps == 0 computes the controls only (x and sat_steps untouched).                    */
+int fdyn_lqr_step_f64(double* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params,
+                      int n_types, int64_t n, double dt, int n_steps, double* surf_out, int32_t* sat_steps, void* stream);
+int fdyn_lqr_step_mixed(double* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params,
+                        int n_types, int64_t n, double dt, int n_steps, double* surf_out, int32_t* sat_steps, void* stream);
+int fdyn_lqr_step_f32(float* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params,
+                      int n_types, int64_t n, double dt, int n_steps, float* surf_out, int32_t* sat_steps, void* stream);
+
+
 /* ---- sensor layer (csrc/sensor_kernels.hip) ---------------------------------------------------------------------------
  * NoisySensorInterface.update (interfaces/sensor.py:199-243) for n aircraft: meas [FD_NMS][n] = the 12 state words +
  * airspeed + altitude with Gaussian noise, body rates additionally offset by the gyro bias; bias [FD_NSB][n]

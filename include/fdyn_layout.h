@@ -256,6 +256,19 @@ enum {
 /* the longitudinal (u, w, q, theta | elevator, throttle) and lateral (v, p, r, phi | aileron, rudder) sub-systems are read
  * out of A [FD_NX * FD_NX][n] and B [FD_NX * FD_NU][n] on the host (hcrl_amd.trim)                                       */
 
+/* ---- gain-scheduled LQR (fdyn_lqr_design / fdyn_lqr_step_*, csrc/lqr_kernels.hip) ------------------------------------- */
+/* weights [FD_NLQW] fp64, all diagonal penalties: q of (u, w, q, theta), q of (v, p, r, phi), r of (elevator, throttle),
+ * r of (aileron, rudder)                                                                                                */
+enum { FD_LQW_Q_LON = 0, FD_LQW_Q_LAT = 4, FD_LQW_R_LON = 8, FD_LQW_R_LAT = 10, FD_NLQW = 12 };
+/* gains K [FD_NLQK][n] fp64: K_lon 2 x 4 row-major (rows elevator, throttle; columns u, w, q, theta), then K_lat 2 x 4
+ * (rows aileron, rudder; columns v, p, r, phi)                                                                          */
+enum { FD_LQK_LON = 0, FD_LQK_LAT = 8, FD_NLQK = 16 };
+/* status bits of a design; 0 = a CERTIFIED stabilising gain
+ *   NOT_CONVERGED   the doubling iteration hit its cap, a singular pivot or a non-finite value
+ *   NO_CERTIFICATE  X is not positive definite or the Riccati residual exceeds 1e-8
+ *   BAD_INPUT       a word of the two blocks of A, B is not finite, or a weight is not finite and > 0: nothing was solved   */
+enum { FD_LQR_NOT_CONVERGED = 1, FD_LQR_NO_CERTIFICATE = 2, FD_LQR_BAD_INPUT = 4 };
+
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
 enum {
