@@ -9,48 +9,23 @@
 // read + one write of the state.  Episode ends are compacted with a wave ballot + mbcnt prefix and ONE
 // atomic per wave into a dense event list (terminal observation, return, length) -- the only inter-lane
 // communication in the path; there is no inter-workgroup communication at all.
+// What the other fleet files (lqr_kernels.hip, trim_kernels.hip) need as well -- parameter staging, lane type, glue type, the
+// entry checks and the launch -- is in fdyn_fleet.hpp; the staging helpers that remain here are the rate env's own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
-#include "fdyn_core.hpp"
-#include "../../include/fdyn.h"
+#include "fdyn_fleet.hpp"
 
 using namespace fdyn;
 
 #define FD_BLOCK 256
-#define FD_MAX_TYPES 8
-#define FD_WAVE 64
 
 // ---------------------------------------------------------------------------------------------------------
-// LDS staging helpers
+// LDS staging helpers of the rate env (stage, stage_params: fdyn_fleet.hpp)
 // ---------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ void stage(T* dst, const T* __restrict__ src, int n)
-{
-    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-}
-
-// Parameter blocks -> LDS: the FD_NP_USED caller words are copied; meanwhile a few threads per aircraft type fill the block's
-// derived words straight from global memory, one word per lane (Params::derive_lane).  One barrier (the caller's).  Kernels
-// issue their per-aircraft global loads BEFORE calling this, so the HBM round trip of the state overlaps the staging chain
-// (global -> LDS -> barrier -> LDS -> registers) instead of following it.
-template <bool FAST>
-__device__ __forceinline__ void stage_params(double* s_params, const double* __restrict__ params, int n_types)
-{
-    for (int i = threadIdx.x; i < n_types * FD_NP_USED; i += blockDim.x) {
-        const int t = i / FD_NP_USED, k = i - t * FD_NP_USED;
-        s_params[t * FD_NP_STAGED + k] = params[t * FD_NP + k];
-    }
-    constexpr int NDL = Params<double>::FD_ND_LANES;
-    if (int(threadIdx.x) < n_types * NDL) {
-        const int t = threadIdx.x / NDL;
-        Params<double>::derive_lane<FAST>(threadIdx.x - t * NDL, params + t * FD_NP, s_params + t * FD_NP_STAGED);
-    }
-}
-
-// The same in two halves, for a kernel whose launch is one burst of per-aircraft loads (the env step at one wave per SIMD): loads
+// stage_params in two halves, for a kernel whose launch is one burst of per-aircraft loads (the env step at one wave per SIMD): loads
 // return IN ORDER, so a parameter word requested after the state is not in LDS -- and the barrier not passed -- before the whole
 // burst has landed.  `early` issues the block's loads FIRST; `finish` stores them once they are back, ahead of the state.
 struct StagedParamWords { double v0, v1, d; };
@@ -122,12 +97,6 @@ __device__ __forceinline__ LaneMap lane_map(int64_t n)
     m.wave_first = m.i - m.lane;
     m.on = m.i < n;
     return m;
-}
-
-__device__ __forceinline__ int lane_type(const uint8_t* __restrict__ type, int64_t i, int n_types)
-{
-    int t = type ? int(type[i]) : 0;
-    return t < n_types ? t : n_types - 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -213,18 +182,13 @@ pid_batch_kernel(const float* __restrict__ cfg /*[8] shared or [n][8]*/, int cfg
 // K1+K2: n_steps control steps of the 5-level cascade + one RK4 each
 //        (examples/03_waypoint_square_demo.py:148-209 per aircraft; agents in fdyn_core.hpp)
 // ---------------------------------------------------------------------------------------------------------
-// Glue type of the agents: the storage type for the fp64 parity variant, the COMPUTE type for the fp32-evaluation variants
-// (their PIDs take fp32 inputs anyway; round 1 ran the glue in fp64 -- ocml sincos / atan2 / fmod several times per control
-// step -- and the glue cost more than the physics: 7.3 us per control step of which 3.1 us were the RK4).
 // Storage type of the 21 env words (`e`): the state's storage type in the f64 and f32 variants, fp32 in `mixed` -- they are
-// commands, previous actions and reward-tracker state, computed in fp32 there anyway (GlueOf below); as fp64 rows they were
+// commands, previous actions and reward-tracker state, computed in fp32 there anyway (GlueOf, fdyn_fleet.hpp); as fp64 rows they were
 // 272 of the 660 bytes an env step moves.  Two words are kept exact in fp32 form: the settling timer counts STEPS (fp32
 // holds small integers exactly; the threshold is the step count at which the reference's accumulated fp64 sum reaches 0.2 s)
 // and the episode time is step * dt rather than an accumulated fp32 sum.
 template <typename S, typename T> struct EnvOf { using type = S; };
 template <> struct EnvOf<double, float> { using type = float; };
-template <typename S, typename T> struct GlueOf { using type = S; };
-template <typename S> struct GlueOf<S, float> { using type = float; };
 
 // (FD_BLOCK, 1): nine PID configurations, 27 PID states, the constants and the integrator state are ~250 live registers;
 // under the default occupancy target the allocator parked part of them in AGPRs and paid ~80 v_accvgpr moves per control step
@@ -1345,22 +1309,6 @@ static int simd_count()
     return g_simds;
 }
 
-// every kernel of this file is launched the same way: one lane per row, FD_BLOCK lanes per workgroup, no dynamic LDS
-template <typename K, typename... A>
-static int launch(K kernel, int64_t n, void* stream, A... args)
-{
-    hipLaunchKernelGGL(kernel, dim3(unsigned((n + FD_BLOCK - 1) / FD_BLOCK)), dim3(FD_BLOCK), 0, (hipStream_t)stream, args...);
-    return int(hipGetLastError());
-}
-
-#define FD_CHECK_COMMON(n, n_types)                                       \
-    if ((n) < 0 || (n) > (int64_t(1) << 31) - FD_BLOCK) return FDYN_ERR_BAD_SIZE;   \
-    if ((n_types) < 1 || (n_types) > FD_MAX_TYPES) return FDYN_ERR_BAD_TYPES;       \
-    if ((n) == 0) return FDYN_OK;
-
-// simplified_6dof.py:241-245: dt <= min_timestep or > max_timestep raises ValueError (defaults)
-static inline bool bad_dt(double dt) { return !(dt > 1e-6) || dt > 1.0; }
-
 // The rate env's reset and step, plain and with domain randomisation (DRA = S* dr [FD_NDR][n], const double* dr_consts [FD_NDC]):
 // the parameters they share are spelled once, the entry points below forward to one host function each.
 #define FD_ENV_RESET_PARAMS(S, E)                                                                            \
@@ -1382,16 +1330,16 @@ template <typename S, typename E, typename... DRA>
 static int env_reset(FD_ENV_RESET_PARAMS(S, E), void* stream, DRA... dra)
 {
     if ((... || !dra)) return FDYN_ERR_NULL;
-    FD_CHECK_COMMON(n, 1)
+    FD_CHECK_FLEET(n, 1, FD_BLOCK)
     if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;
-    return launch(rate_env_reset_kernel<S, E, DRA...>, n, stream, FD_ENV_RESET_ARGS, dra...);
+    return launch<FD_BLOCK>(rate_env_reset_kernel<S, E, DRA...>, n, stream, FD_ENV_RESET_ARGS, dra...);
 }
 
 template <typename S, typename E, typename T, bool PREP, typename... DRA>
 static int env_step(FD_ENV_STEP_PARAMS(S, E), void* stream, DRA... dra)
 {
     if ((... || !dra)) return FDYN_ERR_NULL;
-    FD_CHECK_COMMON(n, n_types)
+    FD_CHECK_FLEET(n, n_types, FD_BLOCK)
     if (pool && pool_depth < 1) return FDYN_ERR_BAD_SIZE;
     if ((!actions || residual_scale > 0.0f) && !(pid_state && pid_cfg && casc_consts)) return FDYN_ERR_NULL;
     if (!obs_out || !terminated || !truncated || !env_consts) return FDYN_ERR_NULL;
@@ -1403,8 +1351,8 @@ static int env_step(FD_ENV_STEP_PARAMS(S, E), void* stream, DRA... dra)
     // never register-capped: its flag is false on both sides, no fp64 OCC2 instantiation)
     constexpr bool FP32 = sizeof(T) == 4;
     const bool occ2 = FP32 && n > int64_t(simd_count()) * FD_WAVE;
-    return launch(occ2 ? rate_env_step_kernel<S, T, FP32, PREP, DRA...> : rate_env_step_kernel<S, T, false, PREP, DRA...>, n, stream,
-                  FD_ENV_STEP_ARGS, dra...);
+    return launch<FD_BLOCK>(occ2 ? rate_env_step_kernel<S, T, FP32, PREP, DRA...> : rate_env_step_kernel<S, T, false, PREP, DRA...>,
+                            n, stream, FD_ENV_STEP_ARGS, dra...);
 }
 
 extern "C" {
@@ -1442,11 +1390,12 @@ int fdyn_device_info(int* cu_count, int* wave_size, char* arch, int arch_len)
     int NAME(S* x, const S* u, const uint8_t* type, const double* params, int n_types, int64_t n, double dt, \
              int n_sub, S* derived_out, void* stream)                                                        \
     {                                                                                                        \
-        FD_CHECK_COMMON(n, n_types)                                                                          \
+        FD_CHECK_FLEET(n, n_types, FD_BLOCK)                                                                 \
         if (n_sub < 1) return FDYN_ERR_BAD_SIZE;                                                             \
         const double dt_sub = dt / n_sub;                                                                    \
         if (bad_dt(dt_sub)) return FDYN_ERR_BAD_DT;                                                          \
-        return launch(sixdof_step_kernel<S, T>, n, stream, x, u, type, params, n_types, n, S(dt_sub), n_sub, derived_out); \
+        return launch<FD_BLOCK>(sixdof_step_kernel<S, T>, n, stream, x, u, type, params, n_types, n, S(dt_sub), n_sub,   \
+                                derived_out);                                                                \
     }
 FD_DEFINE_SIXDOF(fdyn_sixdof_step_f64, double, double)
 FD_DEFINE_SIXDOF(fdyn_sixdof_step_mixed, double, float)
@@ -1454,20 +1403,20 @@ FD_DEFINE_SIXDOF(fdyn_sixdof_step_f32, float, float)
 
 int fdyn_derived_f64(const double* x, int64_t n, double* out, void* stream)
 {
-    FD_CHECK_COMMON(n, 1)
-    return launch(derived_kernel<double>, n, stream, x, n, out);
+    FD_CHECK_FLEET(n, 1, FD_BLOCK)
+    return launch<FD_BLOCK>(derived_kernel<double>, n, stream, x, n, out);
 }
 int fdyn_derived_f32(const float* x, int64_t n, float* out, void* stream)
 {
-    FD_CHECK_COMMON(n, 1)
-    return launch(derived_kernel<float>, n, stream, x, n, out);
+    FD_CHECK_FLEET(n, 1, FD_BLOCK)
+    return launch<FD_BLOCK>(derived_kernel<float>, n, stream, x, n, out);
 }
 
 int fdyn_pid_compute_batch(const float* cfg, int cfg_per_lane, float* state, const float* setpoint,
                            const float* measurement, float dt, float* out, int64_t n, void* stream)
 {
-    FD_CHECK_COMMON(n, 1)
-    return launch(pid_batch_kernel, n, stream, cfg, cfg_per_lane, state, setpoint, measurement, dt, out, n);
+    FD_CHECK_FLEET(n, 1, FD_BLOCK)
+    return launch<FD_BLOCK>(pid_batch_kernel, n, stream, cfg, cfg_per_lane, state, setpoint, measurement, dt, out, n);
 }
 
 #define FD_DEFINE_CASCADE(NAME, S, T)                                                                        \
@@ -1475,23 +1424,23 @@ int fdyn_pid_compute_batch(const float* cfg, int cfg_per_lane, float* state, con
              const float* pid_cfg, const double* consts, const double* wps, int n_wp, int64_t n, double dt,  \
              int n_steps, S* surf_out, int32_t* reached_total, void* stream)                                 \
     {                                                                                                        \
-        FD_CHECK_COMMON(n, n_types)                                                                          \
+        FD_CHECK_FLEET(n, n_types, FD_BLOCK)                                                                 \
         if (n_wp < 1 || n_wp > FD_MAX_WAYPOINTS || n_steps < 0) return FDYN_ERR_BAD_SIZE;                    \
         if (bad_dt(dt)) return FDYN_ERR_BAD_DT;                                                              \
-        return launch(cascade_step_kernel<S, T>, n, stream, x, pid_state, wp_idx, type, params, n_types, pid_cfg, consts, \
-                      wps, n_wp, n, S(dt), n_steps, surf_out, reached_total);                                \
+        return launch<FD_BLOCK>(cascade_step_kernel<S, T>, n, stream, x, pid_state, wp_idx, type, params, n_types, pid_cfg, \
+                                consts, wps, n_wp, n, S(dt), n_steps, surf_out, reached_total);              \
     }
 #define FD_DEFINE_AGENT(NAME, S, T)                                                                          \
     int NAME(int level, S* x, float* pid_state, const uint8_t* type, const double* params, int n_types,      \
              const float* pid_cfg, int cfg_per_lane, const double* consts, const S* cmd, int64_t n, double dt, \
              int n_steps, S* surf_out, void* stream)                                                         \
     {                                                                                                        \
-        FD_CHECK_COMMON(n, n_types)                                                                          \
+        FD_CHECK_FLEET(n, n_types, FD_BLOCK)                                                                 \
         if (level < FD_LEVEL_WAYPOINT || level > FD_LEVEL_RATE || n_steps < 0) return FDYN_ERR_BAD_SIZE;     \
         if (n > 0 && (!x || !pid_state || !pid_cfg || !consts || !cmd)) return FDYN_ERR_NULL;                \
         if (bad_dt(dt)) return FDYN_ERR_BAD_DT;                                                              \
-        return launch(agent_step_kernel<S, T>, n, stream, level, x, pid_state, type, params, n_types, pid_cfg, consts, cmd, \
-                      n, S(dt), n_steps, surf_out, cfg_per_lane);                                            \
+        return launch<FD_BLOCK>(agent_step_kernel<S, T>, n, stream, level, x, pid_state, type, params, n_types, pid_cfg, \
+                                consts, cmd, n, S(dt), n_steps, surf_out, cfg_per_lane);                     \
     }
 FD_DEFINE_AGENT(fdyn_agent_step_f64, double, double)
 FD_DEFINE_AGENT(fdyn_agent_step_mixed, double, float)
@@ -1503,7 +1452,7 @@ FD_DEFINE_AGENT(fdyn_agent_step_f32, float, float)
              const uint8_t* learned, int throttle_src, float* prev_action, float* obs_out, float* rate_cmd_out,  \
              S* surf_out, int32_t* reached_total, int64_t n, double dt, void* stream)                         \
     {                                                                                                        \
-        FD_CHECK_COMMON(n, n_types)                                                                          \
+        FD_CHECK_FLEET(n, n_types, FD_BLOCK)                                                                 \
         if (level != FD_LEVEL_WAYPOINT && level != FD_LEVEL_HSA && level != FD_LEVEL_ATTITUDE) return FDYN_ERR_BAD_SIZE; \
         if (throttle_src != FD_HYBRID_THROTTLE_POLICY && throttle_src != FD_HYBRID_THROTTLE_OUTER) return FDYN_ERR_BAD_SIZE; \
         if (wps && (level != FD_LEVEL_WAYPOINT || n_wp < 1 || n_wp > FD_MAX_WAYPOINTS || cmd)) return FDYN_ERR_BAD_SIZE; \
@@ -1512,9 +1461,9 @@ FD_DEFINE_AGENT(fdyn_agent_step_f32, float, float)
             return FDYN_ERR_NULL;                                                                            \
         if (wps ? !wp_idx : !cmd) return FDYN_ERR_NULL;                                                      \
         if (bad_dt(dt)) return FDYN_ERR_BAD_DT;                                                              \
-        return launch(hybrid_step_kernel<S, T>, n, stream, level, x, pid_state, wp_idx, type, params, n_types, pid_cfg, \
-                      consts, cmd, wps, n_wp, actions, learned, throttle_src, prev_action, obs_out, rate_cmd_out, surf_out, \
-                      reached_total, n, S(dt));                                                              \
+        return launch<FD_BLOCK>(hybrid_step_kernel<S, T>, n, stream, level, x, pid_state, wp_idx, type, params, n_types, \
+                                pid_cfg, consts, cmd, wps, n_wp, actions, learned, throttle_src, prev_action, obs_out, \
+                                rate_cmd_out, surf_out, reached_total, n, S(dt));                            \
     }
 FD_DEFINE_HYBRID(fdyn_hybrid_step_f64, double, double)
 FD_DEFINE_HYBRID(fdyn_hybrid_step_mixed, double, float)
@@ -1548,8 +1497,8 @@ int fdyn_rate_env_image(const double* params, int n_types, const double* env_con
 {
     if (n_types < 1 || n_types > FD_MAX_TYPES) return FDYN_ERR_BAD_TYPES;
     if (!params || !env_consts || !image) return FDYN_ERR_NULL;
-    return launch(fp32_eval ? rate_env_image_kernel<true> : rate_env_image_kernel<false>, FD_BLOCK, stream, params, n_types,
-                  env_consts, image);
+    return launch<FD_BLOCK>(fp32_eval ? rate_env_image_kernel<true> : rate_env_image_kernel<false>, FD_BLOCK, stream, params,
+                            n_types, env_consts, image);
 }
 #define FD_DEFINE_ENV_IMG(SUFFIX, S, E, T)                                                                   \
     int fdyn_rate_env_step_img_##SUFFIX(FD_ENV_STEP_PARAMS(S, E), const double* image, void* stream)         \

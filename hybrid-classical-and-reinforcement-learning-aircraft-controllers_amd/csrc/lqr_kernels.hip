@@ -11,10 +11,12 @@
 // two blocks go through ONE rolled loop, so the solver is inlined once, and what depends on the block -- which rows of A and B,
 // which weights, which half of K -- is a scalar offset into global memory or a select.  64-thread workgroups: 65 536 aircraft
 // are 1024 waves, one per SIMD, each with the whole register file.
+// Shared with the other fleet files: the 4 x 4 inverses are fdyn_dense.hpp's elimination (the one trim_kernels.hip solves its
+// Newton step with); parameter staging, lane type, glue type, entry checks and launch are fdyn_fleet.hpp's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "fdyn_core.hpp"
-#include "../../include/fdyn.h"
+#include "fdyn_fleet.hpp"
+#include "fdyn_dense.hpp"
 
 using namespace fdyn;
 
@@ -22,24 +24,11 @@ namespace {
 
 constexpr int TB = 64;                   // design: threads per workgroup
 constexpr int SB = 256;                  // step: threads per workgroup, as every fleet kernel of fdyn_kernels.hip
-constexpr int MAX_TYPES = 8;
 constexpr int NB = 4;                    // states per block
 constexpr int LQR_MAX_ITERS = 30;
 constexpr double LQR_TOL = 1e-13, LQR_PIVOT_REL = 1e-14, LQR_RES_MAX = 1e-8;
 
 struct M4 { double v[NB][NB]; };
-
-FD_DEV double worse(double m, double v) { return (v > m || v != v) ? v : m; }     // max, NaN wins and stays
-
-FD_DEV double max_abs(const M4& a)
-{
-    double m = 0.0;
-#pragma unroll
-    for (int r = 0; r < NB; ++r)
-#pragma unroll
-        for (int c = 0; c < NB; ++c) m = worse(m, ::fabs(a.v[r][c]));
-    return m;
-}
 
 // a b, a^T b, a b^T: every element summed k = 0..3 in that order, no contraction
 template <bool TA, bool TBB>
@@ -59,53 +48,15 @@ FD_DEV M4 mul(const M4& a, const M4& b)
     return c;
 }
 
-// a^-1 by elimination with partial pivoting on [a | I] and back substitution, every index a compile-time constant, row swaps
-// as selects.  Returns false (singular) when a pivot is below LQR_PIVOT_REL * max|a| or not a number.
+// a^-1: fdyn_dense.hpp's elimination on [a | I].  False (singular) when a pivot is below LQR_PIVOT_REL * max|a| or not a number.
 FD_DEV bool inverse(M4 a, M4& x)
 {
-#pragma clang fp contract(off)
-    const double floor_ = LQR_PIVOT_REL * max_abs(a);
     M4 b;
 #pragma unroll
     for (int r = 0; r < NB; ++r)
 #pragma unroll
         for (int c = 0; c < NB; ++c) b.v[r][c] = r == c ? 1.0 : 0.0;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        int p = k;
-        double best = ::fabs(a.v[k][k]);
-#pragma unroll
-        for (int r = k + 1; r < NB; ++r) { const double v = ::fabs(a.v[r][k]); const bool t = v > best; best = t ? v : best; p = t ? r : p; }
-#pragma unroll
-        for (int r = k + 1; r < NB; ++r) {
-            const bool sw = p == r;
-#pragma unroll
-            for (int c = k; c < NB; ++c) { const double t = a.v[k][c]; a.v[k][c] = sw ? a.v[r][c] : t; a.v[r][c] = sw ? t : a.v[r][c]; }
-#pragma unroll
-            for (int c = 0; c < NB; ++c) { const double t = b.v[k][c]; b.v[k][c] = sw ? b.v[r][c] : t; b.v[r][c] = sw ? t : b.v[r][c]; }
-        }
-        ok = ok && (best >= floor_) && (best > 0.0);             // false for NaN
-        const double piv = a.v[k][k];
-#pragma unroll
-        for (int r = k + 1; r < NB; ++r) {
-            const double m = a.v[r][k] / piv;
-#pragma unroll
-            for (int c = k + 1; c < NB; ++c) a.v[r][c] = a.v[r][c] - m * a.v[k][c];
-#pragma unroll
-            for (int c = 0; c < NB; ++c) b.v[r][c] = b.v[r][c] - m * b.v[k][c];
-        }
-    }
-#pragma unroll
-    for (int k = NB - 1; k >= 0; --k)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            double s = b.v[k][j];
-#pragma unroll
-            for (int c = k + 1; c < NB; ++c) s = s - a.v[k][c] * x.v[c][j];
-            x.v[k][j] = s / a.v[k][k];
-        }
-    return ok;
+    return gauss_solve<NB, NB>(a.v, b.v, x.v, LQR_PIVOT_REL);
 }
 
 // x = L D L^T with every d > 0 <=> x is positive definite (a Cholesky factorisation without the square roots)
@@ -239,7 +190,7 @@ lqr_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __res
                 }
             Ak = A1;
             ++it;
-            const double hmax = max_abs(Hk), diff = max_abs(dif);
+            const double hmax = max_abs(Hk.v), diff = max_abs(dif.v);
             if (!(::isfinite(hmax) && ::isfinite(diff))) { failed = true; break; }
             converged = diff <= LQR_TOL * (hmax > 1.0 ? hmax : 1.0);
         }
@@ -270,9 +221,9 @@ lqr_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __res
                 const double t = (AtX.v[r][c] + Xa.v[r][c]) - XGX.v[r][c];
                 R.v[r][c] = r == c ? t + q[r] : t;
             }
-        const double xmax = max_abs(X);
-        const double bres = max_abs(R) / (xmax > 1.0 ? xmax : (xmax == xmax ? 1.0 : xmax));
-        res = worse(res, bres);
+        const double xmax = max_abs(X.v);
+        const double bres = max_abs(R.v) / (xmax > 1.0 ? xmax : (xmax == xmax ? 1.0 : xmax));
+        res = nan_max(res, bres);
         it_max = it > it_max ? it : it_max;
         if (failed || !converged) st |= FD_LQR_NOT_CONVERGED;
         if (!positive_definite(X) || !(bres <= LQR_RES_MAX)) st |= FD_LQR_NO_CERTIFICATE;
@@ -287,33 +238,6 @@ lqr_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __res
 }
 
 // ---- the closed loop ------------------------------------------------------------------------------------------------------------
-// The helpers below restate, word for word, what fdyn_kernels.hip keeps file-local for agent_step_kernel: parameter staging,
-// the lane map, the glue type.
-
-template <bool FAST>
-FD_DEV void stage_params(double* s_params, const double* __restrict__ params, int n_types)
-{
-    for (int i = threadIdx.x; i < n_types * FD_NP_USED; i += blockDim.x) {
-        const int t = i / FD_NP_USED, k = i - t * FD_NP_USED;
-        s_params[t * FD_NP_STAGED + k] = params[t * FD_NP + k];
-    }
-    constexpr int NDL = Params<double>::FD_ND_LANES;
-    if (int(threadIdx.x) < n_types * NDL) {
-        const int t = threadIdx.x / NDL;
-        Params<double>::derive_lane<FAST>(threadIdx.x - t * NDL, params + t * FD_NP, s_params + t * FD_NP_STAGED);
-    }
-}
-
-FD_DEV int lane_type(const uint8_t* __restrict__ type, int64_t i, int n_types)
-{
-    int t = type ? int(type[i]) : 0;
-    return t < n_types ? t : n_types - 1;
-}
-
-// glue type of the control law: the storage type for the fp64 parity variant, fp32 for the fp32-evaluation variants
-template <typename S, typename T> struct GlueOf { using type = S; };
-template <typename S> struct GlueOf<S, float> { using type = float; };
-
 // u = u0 - K delta for one lane.  The eight differences x - x0 are formed in fp64 from the stored state (exact to the
 // state's own rounding, whatever the variant), then everything runs in the glue type.
 template <typename G> struct LqrLaw {
@@ -360,7 +284,7 @@ lqr_step_kernel(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*
 {
     using G = typename GlueOf<S, T>::type;
     constexpr bool FAST = sizeof(T) == 4;
-    __shared__ double s_params[MAX_TYPES * FD_NP_STAGED];
+    __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
     stage_params<FAST>(s_params, params, n_types);
     __syncthreads();
     const int64_t i = int64_t(blockIdx.x) * SB + threadIdx.x;
@@ -421,21 +345,15 @@ lqr_step_kernel(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*
     }
 }
 
-// simplified_6dof.py:241-245: dt <= min_timestep or > max_timestep raises ValueError (defaults)
-inline bool bad_dt(double dt) { return !(dt > 1e-6) || dt > 1.0; }
-
 template <typename S, typename T>
 int launch_step(S* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params, int n_types,
                 int64_t n, double dt, int n_steps, S* surf_out, int32_t* sat_steps, void* stream)
 {
-    if (n < 0 || n > (int64_t(1) << 31) - SB || n_steps < 0) return FDYN_ERR_BAD_SIZE;
-    if (n_types < 1 || n_types > MAX_TYPES) return FDYN_ERR_BAD_TYPES;
-    if (n == 0) return FDYN_OK;
+    if (n_steps < 0) return FDYN_ERR_BAD_SIZE;
+    FD_CHECK_FLEET(n, n_types, SB)
     if (!x || !x0 || !u0 || !K || !params) return FDYN_ERR_NULL;
     if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
-    hipLaunchKernelGGL((lqr_step_kernel<S, T>), dim3(unsigned((n + SB - 1) / SB)), dim3(SB), 0, (hipStream_t)stream, x, x0, u0, K, type,
-                       params, n_types, n, S(dt), n_steps, surf_out, sat_steps);
-    return int(hipGetLastError());
+    return launch<SB>(lqr_step_kernel<S, T>, n, stream, x, x0, u0, K, type, params, n_types, n, S(dt), n_steps, surf_out, sat_steps);
 }
 
 }  // namespace
@@ -445,12 +363,9 @@ extern "C" {
 int fdyn_lqr_design(const double* A, const double* B, const double* weights, int weights_per_lane, int64_t n, double* K,
                     double* residual, int32_t* iters, int32_t* status, void* stream)
 {
-    if (n < 0 || n > (int64_t(1) << 31) - TB) return FDYN_ERR_BAD_SIZE;
-    if (n == 0) return FDYN_OK;
+    FD_CHECK_FLEET(n, 1, TB)
     if (!A || !B || !weights || !K || !residual || !iters || !status) return FDYN_ERR_NULL;
-    hipLaunchKernelGGL(lqr_design_kernel, dim3(unsigned((n + TB - 1) / TB)), dim3(TB), 0, (hipStream_t)stream, A, B, weights,
-                       weights_per_lane, n, K, residual, iters, status);
-    return int(hipGetLastError());
+    return launch<TB>(lqr_design_kernel, n, stream, A, B, weights, weights_per_lane, n, K, residual, iters, status);
 }
 
 int fdyn_lqr_step_f64(double* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params,

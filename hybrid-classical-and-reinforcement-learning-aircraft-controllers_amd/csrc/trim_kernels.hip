@@ -15,43 +15,29 @@
 // difference -- select their element with compare-and-select chains (the Jacobian's columns wait in per-lane LDS slots).  The rolled column loop also keeps ONE inlined copy of
 // the dynamics per use instead of fifteen (each is a few thousand instructions with the fp64 ocml sincos / atan2 / asin).
 // 64-thread workgroups: 65 536 aircraft are 1024 waves, one per SIMD of the chip, each with the whole register file.
+// Shared with the other fleet files: the Newton step is fdyn_dense.hpp's elimination (gauss_solve<7, 1>; lqr_kernels.hip inverts
+// with the same one); parameter staging, lane type and launch are fdyn_fleet.hpp's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "fdyn_core.hpp"
-#include "../../include/fdyn.h"
+#include "fdyn_fleet.hpp"
+#include "fdyn_dense.hpp"
 
 using namespace fdyn;
 
 namespace {
 
 constexpr int TB = 64;                   // threads per workgroup
-constexpr int MAX_TYPES = 8;
 constexpr int NZ = 7;                    // unknowns of the trim problem
 constexpr int TRIM_MAX_ITERS = 20;
 constexpr double TRIM_FD_STEP = 1e-6, TRIM_TOL = 1e-12, TRIM_PIVOT_REL = 1e-14;
 constexpr double LIN_STEP = 1e-5;
 
-// parameter blocks -> LDS at stride FD_NP_STAGED, reciprocals from lanes 0..4 of each type (Params::derive_lane<false>)
-FD_DEV void stage_blocks(double* s_params, const double* __restrict__ params, int n_types)
-{
-    for (int i = threadIdx.x; i < n_types * FD_NP; i += blockDim.x) {
-        const int t = i / FD_NP, k = i - t * FD_NP;
-        if (k < FD_NP_USED) s_params[t * FD_NP_STAGED + k] = params[i];
-    }
-    constexpr int NDL = Params<double>::FD_ND_LANES;
-    static_assert(MAX_TYPES * NDL <= TB, "one derive lane per word and type");
-    if (int(threadIdx.x) < n_types * NDL) {
-        const int t = threadIdx.x / NDL;
-        Params<double>::derive_lane<false>(threadIdx.x - t * NDL, params + t * FD_NP, s_params + t * FD_NP_STAGED);
-    }
-}
+static_assert(FD_MAX_TYPES * Params<double>::FD_ND_LANES <= TB, "stage_params: one derive lane per word and type");
 
 FD_DEV void lane_params(Params<double>& P, const double* s_params, const uint8_t* __restrict__ type,
                         const double* __restrict__ scales, int n_types, int64_t n, int64_t i)
 {
-    int ty = type ? int(type[i]) : 0;
-    ty = ty < n_types ? ty : n_types - 1;
-    P.load(s_params + ty * FD_NP_STAGED);
+    P.load(s_params + lane_type(type, i, n_types) * FD_NP_STAGED);
     if (scales) scale_params<double>(P, scales[0 * n + i], scales[1 * n + i], scales[2 * n + i], scales[3 * n + i], scales[4 * n + i]);
 }
 
@@ -92,59 +78,6 @@ FD_DEV void trim_residual(const Params<double>& P, const TrimSpec& s, double v_s
     F[6] = xd[FD_X_D] + v_sin_gamma;
 }
 
-FD_DEV double max_abs7(const double (&a)[NZ])                // NaN in any element -> NaN
-{
-    double m = 0.0;
-#pragma unroll
-    for (int k = 0; k < NZ; ++k) { const double v = ::fabs(a[k]); m = (v > m || v != v) ? v : m; }
-    return m;
-}
-
-// J dz = rhs by elimination with partial pivoting, every index a compile-time constant, row swaps as selects.
-// Returns false (singular) when a pivot is below TRIM_PIVOT_REL * max|J| or not a number.
-FD_DEV bool solve7(double (&a)[NZ][NZ], double (&b)[NZ], double (&dz)[NZ])
-{
-#pragma clang fp contract(off)
-    double amax = 0.0;
-#pragma unroll
-    for (int r = 0; r < NZ; ++r)
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) { const double v = ::fabs(a[r][c]); amax = (v > amax || v != v) ? v : amax; }
-    const double floor_ = TRIM_PIVOT_REL * amax;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < NZ; ++k) {
-        int p = k;
-        double best = ::fabs(a[k][k]);
-#pragma unroll
-        for (int r = k + 1; r < NZ; ++r) { const double v = ::fabs(a[r][k]); const bool t = v > best; best = t ? v : best; p = t ? r : p; }
-#pragma unroll
-        for (int r = k + 1; r < NZ; ++r) {
-            const bool sw = p == r;
-#pragma unroll
-            for (int c = k; c < NZ; ++c) { const double t = a[k][c]; a[k][c] = sw ? a[r][c] : t; a[r][c] = sw ? t : a[r][c]; }
-            const double t = b[k]; b[k] = sw ? b[r] : t; b[r] = sw ? t : b[r];
-        }
-        ok = ok && (best >= floor_) && (best > 0.0);             // false for NaN
-        const double piv = a[k][k];
-#pragma unroll
-        for (int r = k + 1; r < NZ; ++r) {
-            const double m = a[r][k] / piv;
-#pragma unroll
-            for (int c = k + 1; c < NZ; ++c) a[r][c] = a[r][c] - m * a[k][c];
-            b[r] = b[r] - m * b[k];
-        }
-    }
-#pragma unroll
-    for (int k = NZ - 1; k >= 0; --k) {
-        double s = b[k];
-#pragma unroll
-        for (int c = k + 1; c < NZ; ++c) s = s - a[k][c] * dz[c];
-        dz[k] = s / a[k][k];
-    }
-    return ok;
-}
-
 __global__ void __launch_bounds__(TB)
 trim_kernel(const double* __restrict__ spec /*[5][n]*/, const uint8_t* __restrict__ type, const double* __restrict__ scales /*[5][n]*/,
             const double* __restrict__ params, int n_types, int64_t n, double* __restrict__ x0 /*[12][n]*/,
@@ -152,7 +85,7 @@ trim_kernel(const double* __restrict__ spec /*[5][n]*/, const uint8_t* __restric
             int32_t* __restrict__ status)
 {
 #pragma clang fp contract(off)
-    __shared__ double s_params[MAX_TYPES * FD_NP_STAGED];
+    __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
     // the Jacobian is built one column per pass of a rolled loop: each lane parks its columns in its own LDS slots (the column
     // index is a run-time value there, where it costs nothing) and pulls the finished matrix into registers for the elimination,
     // so the 98 registers of J are not live across the fourteen evaluations that fill it.  No other lane reads these words.
@@ -161,7 +94,7 @@ trim_kernel(const double* __restrict__ spec /*[5][n]*/, const uint8_t* __restric
     const bool on = i < n;
     TrimSpec s{ 1.0, 0.0, 0.0, 0.0, 0.0 };
     if (on) { s.V = spec[0 * n + i]; s.gamma = spec[1 * n + i]; s.psi_dot = spec[2 * n + i]; s.h = spec[3 * n + i]; s.psi0 = spec[4 * n + i]; }
-    stage_blocks(s_params, params, n_types);
+    stage_params<false>(s_params, params, n_types);
     __syncthreads();
     if (!on) return;
     Params<double> P;
@@ -178,7 +111,7 @@ trim_kernel(const double* __restrict__ spec /*[5][n]*/, const uint8_t* __restric
 #pragma unroll 1
         for (;;) {
             trim_residual(P, s, v_sin_gamma, z, F);
-            res = max_abs7(F);
+            res = max_abs(F);
             if (converged || it == TRIM_MAX_ITERS) break;
             if (!::isfinite(res)) { failed = true; break; }
 #pragma unroll 1
@@ -201,18 +134,18 @@ trim_kernel(const double* __restrict__ spec /*[5][n]*/, const uint8_t* __restric
 #pragma unroll
                 for (int r = 0; r < NZ; ++r) s_J[((r * NZ + j) * TB) + threadIdx.x] = (Fp[r] - Fm[r]) / step;
             }
-            double J[NZ][NZ], rhs[NZ], dz[NZ];
+            double J[NZ][NZ], rhs[NZ][1], dz[NZ][1];
 #pragma unroll
             for (int r = 0; r < NZ; ++r)
 #pragma unroll
                 for (int c = 0; c < NZ; ++c) J[r][c] = s_J[((r * NZ + c) * TB) + threadIdx.x];
 #pragma unroll
-            for (int k = 0; k < NZ; ++k) rhs[k] = -F[k];
-            if (!solve7(J, rhs, dz)) { failed = true; break; }
+            for (int k = 0; k < NZ; ++k) rhs[k][0] = -F[k];
+            if (!gauss_solve<NZ, 1>(J, rhs, dz, TRIM_PIVOT_REL)) { failed = true; break; }
 #pragma unroll
-            for (int k = 0; k < NZ; ++k) z[k] = z[k] + dz[k];
+            for (int k = 0; k < NZ; ++k) z[k] = z[k] + dz[k][0];
             ++it;
-            const double step_norm = max_abs7(dz);
+            const double step_norm = max_abs(dz);
             if (!::isfinite(step_norm)) { failed = true; break; }
             converged = step_norm < TRIM_TOL;
         }
@@ -244,7 +177,7 @@ linearize_kernel(const S* __restrict__ xs /*[12][n]*/, const S* __restrict__ us 
                  double* __restrict__ A /*[144][n]*/, double* __restrict__ B /*[48][n]*/)
 {
 #pragma clang fp contract(off)
-    __shared__ double s_params[MAX_TYPES * FD_NP_STAGED];
+    __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
     const int64_t i = int64_t(blockIdx.x) * TB + threadIdx.x;
     const bool on = i < n;
     constexpr int NV = FD_NX + FD_NU;
@@ -257,7 +190,7 @@ linearize_kernel(const S* __restrict__ xs /*[12][n]*/, const S* __restrict__ us 
 #pragma unroll
         for (int k = 0; k < FD_NU; ++k) v[FD_NX + k] = double(us[k * n + i]);
     }
-    stage_blocks(s_params, params, n_types);
+    stage_params<false>(s_params, params, n_types);
     __syncthreads();
     if (!on) return;
     Params<double> P;
@@ -298,9 +231,8 @@ template <typename S>
 int launch_linearize(const void* x, const void* u, const uint8_t* type, const double* scales, const double* params, int n_types,
                      int64_t n, double* A, double* B, void* stream)
 {
-    hipLaunchKernelGGL((linearize_kernel<S>), dim3(unsigned((n + TB - 1) / TB)), dim3(TB), 0, (hipStream_t)stream,
-                       static_cast<const S*>(x), static_cast<const S*>(u), type, scales, params, n_types, n, A, B);
-    return int(hipGetLastError());
+    return launch<TB>(linearize_kernel<S>, n, stream, static_cast<const S*>(x), static_cast<const S*>(u), type, scales, params, n_types,
+                      n, A, B);
 }
 
 }  // namespace
@@ -311,19 +243,17 @@ int fdyn_trim(const double* spec, const uint8_t* type, const double* scales, con
               double* x0, double* u0, double* residual, int32_t* iters, int32_t* status, void* stream)
 {
     if (n < 0) return FDYN_ERR_BAD_SIZE;
-    if (n_types < 1 || n_types > MAX_TYPES) return FDYN_ERR_BAD_TYPES;
+    if (n_types < 1 || n_types > FD_MAX_TYPES) return FDYN_ERR_BAD_TYPES;
     if (n == 0) return FDYN_OK;
     if (!spec || !params || !x0 || !u0 || !residual || !iters || !status) return FDYN_ERR_NULL;
-    hipLaunchKernelGGL(trim_kernel, dim3(unsigned((n + TB - 1) / TB)), dim3(TB), 0, (hipStream_t)stream, spec, type, scales, params,
-                       n_types, n, x0, u0, residual, iters, status);
-    return int(hipGetLastError());
+    return launch<TB>(trim_kernel, n, stream, spec, type, scales, params, n_types, n, x0, u0, residual, iters, status);
 }
 
 int fdyn_linearize(const void* x, const void* u, int xu_f32, const uint8_t* type, const double* scales, const double* params,
                    int n_types, int64_t n, double* A, double* B, void* stream)
 {
     if (n < 0) return FDYN_ERR_BAD_SIZE;
-    if (n_types < 1 || n_types > MAX_TYPES) return FDYN_ERR_BAD_TYPES;
+    if (n_types < 1 || n_types > FD_MAX_TYPES) return FDYN_ERR_BAD_TYPES;
     if (n == 0) return FDYN_OK;
     if (!x || !u || !params || !A || !B) return FDYN_ERR_NULL;
     return xu_f32 ? launch_linearize<float>(x, u, type, scales, params, n_types, n, A, B, stream)

@@ -5,6 +5,8 @@ imports the product package.
 """
 import numpy as np
 
+from trim_numpy import gauss_solve, maxabs
+
 NLQW, NLQK, MAX_ITERS, TOL, PIVOT_REL, RES_MAX = 12, 16, 30, 1e-13, 1e-14, 1e-8
 NOT_CONVERGED, NO_CERTIFICATE, BAD_INPUT = 1, 2, 4
 # rows / columns of the two sub-systems inside A [12][12] and B [12][4] (FD_X_* / FD_U_* numbering)
@@ -21,11 +23,6 @@ def default_weights():
     return 1.0 / (m * m)
 
 
-def maxabs(m):
-    """max |m|, NaN when any element is NaN."""
-    return np.nan if np.isnan(m).any() else float(np.max(np.abs(m)))
-
-
 def mm(a, b):
     """a @ b with every element summed k = 0, 1, 2, ... in that order, one rounding per operation."""
     c = a[:, 0:1] * b[0:1, :]
@@ -35,33 +32,8 @@ def mm(a, b):
 
 
 def inv4(a):
-    """Inverse by elimination with partial pivoting on [a | I], then back substitution -> (inverse, ok); ok is False when a
-    pivot is below PIVOT_REL max|a| or not a number."""
-    a, b = np.array(a, np.float64), np.eye(4)
-    floor = PIVOT_REL * maxabs(a)
-    ok = True
-    old = np.seterr(all="ignore")
-    for k in range(4):
-        p = k
-        best = abs(a[k, k])
-        for r in range(k + 1, 4):
-            if abs(a[r, k]) > best:
-                best, p = abs(a[r, k]), r
-        if p != k:
-            a[[k, p]], b[[k, p]] = a[[p, k]], b[[p, k]]
-        ok = ok and bool(best >= floor) and bool(best > 0.0)
-        for r in range(k + 1, 4):
-            m = a[r, k] / a[k, k]
-            a[r, k + 1:] = a[r, k + 1:] - m * a[k, k + 1:]
-            b[r] = b[r] - m * b[k]
-    x = np.zeros((4, 4))
-    for k in range(3, -1, -1):
-        s = b[k].copy()
-        for c in range(k + 1, 4):
-            s = s - a[k, c] * x[c]
-        x[k] = s / a[k, k]
-    np.seterr(**old)
-    return x, ok
+    """Inverse: trim_numpy's elimination on [a | I] -> (inverse, ok)."""
+    return gauss_solve(a, np.eye(4), PIVOT_REL)
 
 
 def ldl_positive(x):

@@ -22,26 +22,45 @@ def residual(f, spec, z):
     return np.array([xd[3], xd[4], xd[5], xd[9], xd[10], xd[11], xd[2] + spec[0] * np.sin(spec[1])])
 
 
-def solve7(a, b):
-    """Elimination with partial pivoting -> (dz, ok); ok is False when a pivot is below PIVOT_REL max|a| or not a number."""
-    a, b = a.copy(), b.copy()
+def maxabs(m):
+    """max |m|, NaN when any element is NaN."""
+    return np.nan if np.isnan(m).any() else float(np.max(np.abs(m)))
+
+
+def gauss_solve(a, b, pivot_rel=PIVOT_REL):
+    """a x = b, b [n] or [n][m], by elimination with partial pivoting on [a | b], then back substitution -> (x, ok); ok is False
+    when a pivot is below pivot_rel max|a|, is zero or is not a number.  The one elimination of the host models, operation for
+    operation the one of csrc/fdyn_dense.hpp: the first largest |entry| of the column pivots (a NaN never does), every element
+    is a - m * b with m = a[r, k] / pivot, every sum runs left to right."""
+    a, b = np.array(a, np.float64), np.array(b, np.float64)
+    n = len(a)
     with np.errstate(all="ignore"):
-        floor = PIVOT_REL * (np.nan if np.isnan(a).any() else np.max(np.abs(a)))
+        floor = pivot_rel * maxabs(a)
         ok = True
-        for k in range(NZ):
-            p = k + int(np.argmax(np.nan_to_num(np.abs(a[k:, k]), nan=-1.0)))
+        for k in range(n):
+            p, best = k, abs(a[k, k])
+            for r in range(k + 1, n):
+                if abs(a[r, k]) > best:
+                    best, p = abs(a[r, k]), r
             if p != k:
                 a[[k, p]], b[[k, p]] = a[[p, k]], b[[p, k]]
-            best = abs(a[k, k])
             ok = ok and bool(best >= floor) and bool(best > 0.0)
-            for r in range(k + 1, NZ):
+            for r in range(k + 1, n):
                 m = a[r, k] / a[k, k]
                 a[r, k + 1:] = a[r, k + 1:] - m * a[k, k + 1:]
                 b[r] = b[r] - m * b[k]
-        dz = np.zeros(NZ)
-        for k in range(NZ - 1, -1, -1):
-            dz[k] = (b[k] - np.dot(a[k, k + 1:], dz[k + 1:])) / a[k, k]
-    return dz, ok
+        x = np.zeros_like(b)
+        for k in range(n - 1, -1, -1):
+            s = b[k].copy()
+            for c in range(k + 1, n):
+                s = s - a[k, c] * x[c]
+            x[k] = s / a[k, k]
+    return x, ok
+
+
+def solve7(a, b):
+    """The Newton step's 7 x 7 system -> (dz, ok)."""
+    return gauss_solve(a, b, PIVOT_REL)
 
 
 def trim(f, spec, gravity, max_alpha, max_pitch):
