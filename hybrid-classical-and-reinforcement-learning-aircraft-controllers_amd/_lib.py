@@ -18,6 +18,8 @@ _CASCADE = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
 _AGENT = [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]
 _HYBRID = [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i64, _d, _p]
 _LQR_STEP = [_p, _p, _p, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
+# + F, sigma, xhat, du_prev, seed, step, z, feedback, err_est, err_meas, chatter, meas_out before the stream
+_LQG_STEP = _LQR_STEP[:-1] + [_p, _p, _p, _p, _u64, _p, _p, _i, _p, _p, _p, _p, _p]
 _ENV_RESET = [_p, _p, _p, _p, _p, _p, _p, _i, _u64, _p, _i64, _p]
 _ENV_STEP = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _u64, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p,
              _i, _i64, _p]
@@ -87,6 +89,8 @@ SIGNATURES = {
     "fdyn_linearize": (_i, [_p, _p, _i, _p, _p, _p, _i, _i64, _p, _p, _p]),
     "fdyn_lqr_design": (_i, [_p, _p, _p, _i, _i64, _p, _p, _p, _p, _p]),
     "fdyn_lqr_step_f64": (_i, _LQR_STEP), "fdyn_lqr_step_mixed": (_i, _LQR_STEP), "fdyn_lqr_step_f32": (_i, _LQR_STEP),
+    "fdyn_kf_design": (_i, [_p, _p, _d, _p, _i, _i64, _p, _p, _p, _p, _p]),
+    "fdyn_lqg_step_f64": (_i, _LQG_STEP), "fdyn_lqg_step_mixed": (_i, _LQG_STEP), "fdyn_lqg_step_f32": (_i, _LQG_STEP),
 }
 
 _lib = None

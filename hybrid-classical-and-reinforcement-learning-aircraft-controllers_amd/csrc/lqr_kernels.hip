@@ -11,12 +11,17 @@
 // two blocks go through ONE rolled loop, so the solver is inlined once, and what depends on the block -- which rows of A and B,
 // which weights, which half of K -- is a scalar offset into global memory or a select.  64-thread workgroups: 65 536 aircraft
 // are 1024 waves, one per SIMD, each with the whole register file.
-// Shared with the other fleet files: the 4 x 4 inverses are fdyn_dense.hpp's elimination (the one trim_kernels.hip solves its
-// Newton step with); parameter staging, lane type, glue type, entry checks and launch are fdyn_fleet.hpp's.
+// Shared with the other fleet files: the 4 x 4 matrix type, its products, inverse and L D L^T test are fdyn_riccati.hpp's
+// (kf_kernels.hip solves the filter equation with them), on fdyn_dense.hpp's elimination (the one trim_kernels.hip solves its
+// Newton step with); parameter staging, lane type, glue type, entry checks and launch are fdyn_fleet.hpp's.  The doubling loop
+// below is also fdyn_riccati.hpp's riccati_doubling, word for word: called from there this kernel compiled to 44 more
+// instructions and its time left the spread of three runs of the listing below (+1 %), so it keeps the loop in line and
+// the file compiles to the ISA it had before the headers existed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fdyn_fleet.hpp"
-#include "fdyn_dense.hpp"
+#include "fdyn_riccati.hpp"
+#include "fdyn_lqr_law.hpp"
 
 using namespace fdyn;
 
@@ -24,64 +29,8 @@ namespace {
 
 constexpr int TB = 64;                   // design: threads per workgroup
 constexpr int SB = 256;                  // step: threads per workgroup, as every fleet kernel of fdyn_kernels.hip
-constexpr int NB = 4;                    // states per block
-constexpr int LQR_MAX_ITERS = 30;
-constexpr double LQR_TOL = 1e-13, LQR_PIVOT_REL = 1e-14, LQR_RES_MAX = 1e-8;
-
-struct M4 { double v[NB][NB]; };
-
-// a b, a^T b, a b^T: every element summed k = 0..3 in that order, no contraction
-template <bool TA, bool TBB>
-FD_DEV M4 mul(const M4& a, const M4& b)
-{
-#pragma clang fp contract(off)
-    M4 c;
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            double s = (TA ? a.v[0][i] : a.v[i][0]) * (TBB ? b.v[j][0] : b.v[0][j]);
-#pragma unroll
-            for (int k = 1; k < NB; ++k) s = s + (TA ? a.v[k][i] : a.v[i][k]) * (TBB ? b.v[j][k] : b.v[k][j]);
-            c.v[i][j] = s;
-        }
-    return c;
-}
-
-// a^-1: fdyn_dense.hpp's elimination on [a | I].  False (singular) when a pivot is below LQR_PIVOT_REL * max|a| or not a number.
-FD_DEV bool inverse(M4 a, M4& x)
-{
-    M4 b;
-#pragma unroll
-    for (int r = 0; r < NB; ++r)
-#pragma unroll
-        for (int c = 0; c < NB; ++c) b.v[r][c] = r == c ? 1.0 : 0.0;
-    return gauss_solve<NB, NB>(a.v, b.v, x.v, LQR_PIVOT_REL);
-}
-
-// x = L D L^T with every d > 0 <=> x is positive definite (a Cholesky factorisation without the square roots)
-FD_DEV bool positive_definite(const M4& x)
-{
-#pragma clang fp contract(off)
-    double L[NB][NB], d[NB];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        double s = x.v[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k] * d[k];
-        d[j] = s;
-        ok = ok && (s > 0.0);                                    // false for NaN
-#pragma unroll
-        for (int i = j + 1; i < NB; ++i) {
-            double t = x.v[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) t = t - L[i][k] * L[j][k] * d[k];
-            L[i][j] = t / s;
-        }
-    }
-    return ok;
-}
+constexpr int NB = RIC_N;                // states per block
+constexpr double LQR_RES_MAX = RIC_RES_MAX;
 
 __global__ void __launch_bounds__(TB)
 lqr_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __restrict__ B /*[48][n]*/,
@@ -169,7 +118,7 @@ lqr_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __res
         int it = 0;
         bool converged = false;
 #pragma unroll 1
-        while (!failed && !converged && it < LQR_MAX_ITERS) {
+        while (!failed && !converged && it < RIC_MAX_ITERS) {
             M4 Mi, IGH = mul<false, false>(Gk, Hk);
 #pragma unroll
             for (int r = 0; r < NB; ++r) IGH.v[r][r] = 1.0 + IGH.v[r][r];
@@ -192,7 +141,7 @@ lqr_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __res
             ++it;
             const double hmax = max_abs(Hk.v), diff = max_abs(dif.v);
             if (!(::isfinite(hmax) && ::isfinite(diff))) { failed = true; break; }
-            converged = diff <= LQR_TOL * (hmax > 1.0 ? hmax : 1.0);
+            converged = diff <= RIC_TOL * (hmax > 1.0 ? hmax : 1.0);
         }
 
         M4 X;
@@ -237,45 +186,7 @@ lqr_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __res
     status[i] = st;
 }
 
-// ---- the closed loop ------------------------------------------------------------------------------------------------------------
-// u = u0 - K delta for one lane.  The eight differences x - x0 are formed in fp64 from the stored state (exact to the
-// state's own rounding, whatever the variant), then everything runs in the glue type.
-template <typename G> struct LqrLaw {
-    G k[FD_NLQK], u0[FD_NU];
-    double x0[8];                                               // u, w, q, theta | v, p, r, phi of the trim
-    template <typename S>
-    FD_DEV Surfaces<G> operator()(const S (&x)[FD_NX]) const
-    {
-#pragma clang fp contract(off)
-        constexpr int W[8] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL };
-        G d[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            d[j] = G(double(x[W[j]]) - x0[j]);
-            if (j == 3 || j == 7) d[j] = wrap_angle<G>(d[j]);
-        }
-        G s[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int o = (r >> 1) * 4;                          // rows 0, 1: longitudinal words; rows 2, 3: lateral
-            G a = k[r * 4] * d[o];
-#pragma unroll
-            for (int c = 1; c < 4; ++c) a = a + k[r * 4 + c] * d[o + c];
-            s[r] = a;
-        }
-        Surfaces<G> u;
-        u.elevator = u0[FD_U_ELEVATOR] - s[0]; u.throttle = u0[FD_U_THROTTLE] - s[1];
-        u.aileron = u0[FD_U_AILERON] - s[2]; u.rudder = u0[FD_U_RUDDER] - s[3];
-        return u;
-    }
-};
-
-template <typename G> FD_DEV bool any_clipped(const Surfaces<G>& u)
-{
-    return !(u.elevator >= G(-1) && u.elevator <= G(1) && u.aileron >= G(-1) && u.aileron <= G(1)
-             && u.rudder >= G(-1) && u.rudder <= G(1) && u.throttle >= G(0) && u.throttle <= G(1));
-}
-
+// ---- the closed loop (the law u = u0 - K delta is fdyn_lqr_law.hpp's: kf_kernels.hip feeds it an estimate) ---------------------------
 template <typename S, typename T>
 __global__ void __launch_bounds__(SB, 1)
 lqr_step_kernel(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,

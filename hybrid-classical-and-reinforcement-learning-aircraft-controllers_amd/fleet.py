@@ -113,6 +113,7 @@ class BatchedSixDOF:
         out = Q.design_lqr(res, self.params, self.type_index, trim_scales if scales is None else scales, weights)
         if strict:
             Q.require_ok(out, f"{type(self).__name__}.design_lqr")
+        self._lqr = out                                  # the gains step_lqg feeds the estimate to
         return out
 
     def step_lqr(self, design, n_steps: int = 1, dt: Optional[float] = None):
@@ -127,6 +128,41 @@ class BatchedSixDOF:
             self.lqr_saturated_steps = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         Q.step_into(self.precision, self.x, design, self.params, self.type_index, dt, n_steps, self.u, self.lqr_saturated_steps)
         self.time += dt * n_steps
+
+    # LQG (hcrl_amd.lqg): the estimator beside the LQR, and the output-feedback loop on noisy measurements
+    def design_kalman(self, dt: float, noise=None, scales=None, strict: bool = True):
+        """A steady-state Kalman filter for every aircraft at the fleet's current trim, discretised at `dt`: KalmanDesign with
+        F [80][N], status 0 = a certified stable filter.  noise: None (the sensor layer's default noise and the default
+        process-noise rates), a KalmanNoise, or [16] / [16][N]; scales as design_lqr.  strict: raise ValueError when an aircraft
+        has no certified filter.  Also starts the loop's state (`lqg`: estimate at the trim, step word 0)."""
+        from . import lqg as G
+        if self._trim is None:
+            raise ValueError(f"{type(self).__name__}.design_kalman: the fleet has no trim; call .trim(...) first")
+        res, trim_scales = self._trim
+        out = G.design_kalman(res, self.params, self.type_index, trim_scales if scales is None else scales, dt, noise)
+        if strict:
+            G.require_ok(out, f"{type(self).__name__}.design_kalman")
+        self._kalman = out
+        self.lqg = G.LqgState.zeros(self.n, self.device, seed=getattr(self, "seed", 0) or 0)
+        return out
+
+    def step_lqg(self, n_steps: int = 1, feedback: str = "estimate", z=None):
+        """n_steps x {measure the eight regulated words with the sensor noise -> Kalman update -> u = u0 - K f, clipped -> one
+        RK4 of the filter's dt} in ONE launch, f = the estimate, the raw measurement or the true state.  Needs design_lqr()
+        and design_kalman() first.  z: None = in-kernel Philox draws keyed by `lqg.seed` and `lqg.step`, or [n_steps][8][N]
+        float64 standard normals.  `u` receives the last applied controls, `lqr_saturated_steps` counts clipped steps, `lqg`
+        carries the estimate and the accumulators (err_est, err_meas, chatter)."""
+        from . import lqg as G
+        lqr_design, kalman = getattr(self, "_lqr", None), getattr(self, "_kalman", None)
+        if lqr_design is None or kalman is None:
+            missing = "design_lqr()" if lqr_design is None else "design_kalman(dt)"
+            raise ValueError(f"{type(self).__name__}.step_lqg: {self.n} of {self.n} aircraft have no certified "
+                             f"{'stabilising gain' if lqr_design is None else 'stable filter'} (call .{missing} first)")
+        if getattr(self, "lqr_saturated_steps", None) is None:
+            self.lqr_saturated_steps = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        G.step_into(self.precision, self.x, lqr_design, kalman, self.lqg, self.params, self.type_index, kalman.dt, n_steps, feedback, z,
+                    self.u, self.lqr_saturated_steps)
+        self.time += kalman.dt * n_steps
 
 
 class BatchedCascade(BatchedSixDOF):

@@ -1,0 +1,223 @@
+"""LQG for whole fleets: the estimator beside `hcrl_amd.lqr`'s regulator -- trim -> linearise -> design (gain AND filter) -> fly on
+noisy sensors.
+
+`fdyn_kf_design` (csrc/kf_kernels.hip) gives every aircraft the steady-state discrete Kalman filter of its own linear model
+at a step `dt` -- the dual Riccati problem, solved by the loop `fdyn_lqr_design` runs -- and `fdyn_lqg_step_*` flies the
+output-feedback loop in one launch: the eight regulated words are measured with the sensor layer's noise, filtered, and the
+LQR law is fed the estimate.
+
+    fleet = BatchedSixDOF(65536, "mixed", types=("rc_plane", "cessna"), type_index=idx)
+    fleet.trim(20.0)
+    fleet.design_lqr()
+    fleet.design_kalman(dt=0.01)                 # KalmanDesign: F [80][n], status 0 = a certified stable filter
+    fleet.step_lqg(100)                          # feedback="estimate" | "measurement" | "truth"
+
+Nothing here synchronises with the device except `count_not_ok` and `require_ok`, which read results back on purpose.
+"""
+from dataclasses import dataclass, field
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib, layout as L
+from . import lqr as Q
+from . import trim as T
+from .sensors import noise_block
+
+STATUS_BITS = ((L.FD_KF_NOT_CONVERGED, "not converged"), (L.FD_KF_NO_CERTIFICATE, "no stability certificate"),
+               (L.FD_KF_BAD_INPUT, "invalid model, noise or dt"))
+FEEDBACK = {"estimate": L.FD_LQG_ESTIMATE, "measurement": L.FD_LQG_MEASUREMENT, "truth": L.FD_LQG_TRUTH}
+DEFAULT_RATES = (0.1, 0.1, 0.05, 0.005, 0.1, 0.05, 0.05, 0.005)     # s of (u, w, q, theta | v, p, r, phi), state units per sqrt(s)
+
+
+def describe_status(status: int) -> str:
+    """'ok' or the names of the FD_KF_* bits set in one status word."""
+    names = [name for bit, name in STATUS_BITS if int(status) & bit]
+    return ", ".join(names) if names else "ok"
+
+
+def sensor_sigma(noise_config: Optional[dict] = None) -> np.ndarray:
+    """[8] float64: the sensor layer's standard deviations on (u, w, q, theta | v, p, r, phi) -- GPS velocity on the body
+    velocities, gyro on the rates, attitude on the two angles -- from a `NoisySensorInterface` noise_config (None: its defaults)."""
+    c = noise_block(noise_config)
+    vel, gyro, att = c[L.FD_SN_GPS_VEL], c[L.FD_SN_GYRO], c[L.FD_SN_ATTITUDE]
+    return np.array([vel, vel, gyro, att, vel, gyro, gyro, att], dtype=np.float64)
+
+
+@dataclass
+class KalmanNoise:
+    """What the filter is designed for: the measurement standard deviations (from a sensor noise_config, or given) and the
+    process-noise rates s in state units per sqrt(s).  Every entry of `sigma` and `rates` a scalar, or a length-n array for a
+    sweep in one launch (`rows`)."""
+    noise_config: Optional[dict] = None
+    sigma: Optional[tuple] = None              # 8 entries; None: sensor_sigma(noise_config)
+    rates: tuple = DEFAULT_RATES
+
+    def _entries(self):
+        sigma = tuple(sensor_sigma(self.noise_config)) if self.sigma is None else tuple(self.sigma)
+        rates = tuple(self.rates)
+        if len(sigma) != 8 or len(rates) != 8:
+            raise ValueError("KalmanNoise: sigma and rates have 8 entries each (u, w, q, theta | v, p, r, phi)")
+        return sigma + rates
+
+    @property
+    def per_lane(self) -> bool:
+        return any(np.ndim(v.detach().cpu() if isinstance(v, torch.Tensor) else v) > 0 for v in self._entries())
+
+    def vector(self) -> np.ndarray:
+        """[FD_NKFN] float64 (every entry a scalar)."""
+        return np.array([float(np.asarray(v).reshape(())) for v in self._entries()], dtype=np.float64)
+
+    def rows(self, n: int) -> np.ndarray:
+        """[FD_NKFN][n] float64: scalars broadcast, length-n arrays taken per aircraft."""
+        return T.broadcast_rows(n, self._entries(), "Kalman noise entry")
+
+
+def noise_tensor(noise, n: int, device) -> torch.Tensor:
+    """None (the defaults), a KalmanNoise, or an array / tensor [FD_NKFN] or [FD_NKFN][n] -> float64 on the device."""
+    if noise is None:
+        noise = KalmanNoise()
+    if isinstance(noise, KalmanNoise):
+        return torch.as_tensor(noise.rows(n) if noise.per_lane else noise.vector(), device=device)
+    w = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(np.asarray(noise, np.float64))
+    if tuple(w.shape) not in ((L.FD_NKFN,), (L.FD_NKFN, n)):
+        raise ValueError(f"noise: expected [{L.FD_NKFN}] or [{L.FD_NKFN}][{n}], got {tuple(w.shape)}")
+    return w.to(device=device, dtype=torch.float64).contiguous()
+
+
+@dataclass
+class KalmanDesign:
+    F: torch.Tensor                         # [80][n] float64: Phi_lon, Phi_lat, Gamma_lon, Gamma_lat, L_lon, L_lat (FD_KF_*)
+    residual: torch.Tensor                  # [n] float64: relative residual of the filter equation, worse block (NaN: invalid input)
+    iters: torch.Tensor                     # [n] int32: doubling steps of the slower block
+    status: torch.Tensor                    # [n] int32: FD_KF_* bits, 0 = a certified stable filter
+    dt: float = 0.0                         # the step the model was discretised at
+    sigma: Optional[torch.Tensor] = None    # [8] float64: the measurement noise the loop applies (shared noise only)
+
+    @property
+    def n(self) -> int:
+        return int(self.status.shape[0])
+
+    @property
+    def ok(self) -> torch.Tensor:
+        return self.status == 0
+
+    def count_not_ok(self) -> int:
+        return int((self.status != 0).sum())
+
+    def _matrix(self, lon: int, lat: int, cols: int) -> torch.Tensor:
+        return torch.stack([self.F[base:base + 4 * cols].reshape(4, cols, self.n) for base in (lon, lat)])
+
+    def phi(self) -> torch.Tensor:
+        """[2][4][4][n]: the discretised longitudinal and lateral blocks."""
+        return self._matrix(L.FD_KF_PHI_LON, L.FD_KF_PHI_LAT, 4)
+
+    def gamma(self) -> torch.Tensor:
+        """[2][4][2][n]: the discretised input matrices (columns elevator, throttle | aileron, rudder)."""
+        return self._matrix(L.FD_KF_GAMMA_LON, L.FD_KF_GAMMA_LAT, 2)
+
+    def gain(self) -> torch.Tensor:
+        """[2][4][4][n]: the steady-state Kalman gains L."""
+        return self._matrix(L.FD_KF_L_LON, L.FD_KF_L_LAT, 4)
+
+    def filter_matrix(self) -> torch.Tensor:
+        """[2][4][4][n]: Phi (I - L), the error dynamics of the filter (Schur where status is 0)."""
+        eye = torch.eye(4, dtype=self.F.dtype, device=self.F.device)[None, :, :, None]
+        return torch.einsum("bikn,bkjn->bijn", self.phi(), eye - self.gain())
+
+
+def kalman_into(A: torch.Tensor, B: torch.Tensor, dt: float, noise: torch.Tensor, out: Optional[KalmanDesign] = None) -> KalmanDesign:
+    """One launch of fdyn_kf_design on device tensors: A [12][12][n], B [12][4][n], noise [16] or [16][n], all float64; with
+    `out` given nothing is allocated (the form to capture in a graph)."""
+    n, dev = int(A.shape[-1]), A.device
+    if tuple(A.shape) != (L.FD_NX, L.FD_NX, n) or tuple(B.shape) != (L.FD_NX, L.FD_NU, n):
+        raise ValueError(f"expected A [12][12][n] and B [12][4][n], got {tuple(A.shape)} and {tuple(B.shape)}")
+    if tuple(noise.shape) not in ((L.FD_NKFN,), (L.FD_NKFN, n)):
+        raise ValueError(f"noise: expected [{L.FD_NKFN}] or [{L.FD_NKFN}][{n}], got {tuple(noise.shape)}")
+    if A.dtype != torch.float64 or B.dtype != torch.float64 or noise.dtype != torch.float64:
+        raise ValueError("A, B and noise must be float64")
+    if out is None:
+        out = KalmanDesign(torch.empty((L.FD_NKF, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                           torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    rc = _lib.load().fdyn_kf_design(_lib.ptr(A), _lib.ptr(B), float(dt), _lib.ptr(noise), int(noise.dim() == 2), n, _lib.ptr(out.F),
+                                    _lib.ptr(out.residual), _lib.ptr(out.iters), _lib.ptr(out.status), _lib.current_stream())
+    _lib.check(rc, "fdyn_kf_design")
+    out.dt = float(dt)
+    return out
+
+
+def design_kalman(trim_result, params: torch.Tensor, type_index=None, scales=None, dt: float = 0.01, noise=None) -> KalmanDesign:
+    """Linearise every aircraft at its trim (fdyn_linearize at x0, u0), then design its filter at step dt.  params, type_index,
+    scales as `lqr.design_lqr` takes them; noise as `noise_tensor` takes it.  The loop's own measurement noise (`sigma`) is the
+    design's when the noise is shared, else the sensor defaults: set `.sigma` to fly another."""
+    n, dev = trim_result.n, trim_result.x0.device
+    A, B = T.linearize_into(trim_result.x0, trim_result.u0, params, T._type_tensor(n, type_index, dev), T.scale_rows(n, scales, dev))
+    nz = noise_tensor(noise, n, dev)
+    out = kalman_into(A, B, dt, nz)
+    out.sigma = nz[:8].clone() if nz.dim() == 1 else torch.as_tensor(sensor_sigma(), device=dev)
+    return out
+
+
+def require_ok(design: KalmanDesign, what: str = "design_kalman"):
+    """ValueError naming how many lanes have no certified filter, and why for the first of them."""
+    bad = design.count_not_ok()
+    if bad:
+        first = int(torch.nonzero(design.status != 0)[0])
+        raise ValueError(f"{what}: {bad} of {design.n} aircraft have no certified stable filter "
+                         f"(first: aircraft {first}: {describe_status(int(design.status[first]))})")
+
+
+@dataclass
+class LqgState:
+    """What the loop carries between launches, all on the device: the estimate, the last applied control offset, the step word
+    that keys the in-kernel draws, and the accumulators the kernel adds to."""
+    xhat: torch.Tensor                      # [8][n] float64: estimate of (u, w, q, theta | v, p, r, phi) - trim
+    du_prev: torch.Tensor                   # [4][n] float64: last applied clipped control - u0
+    step: torch.Tensor                      # [1] int32: steps flown; the draws of step s of a launch are keyed step + s + 1
+    err_est: torch.Tensor                   # [8][n] float64: sum of (xhat - delta)^2
+    err_meas: torch.Tensor                  # [8][n] float64: sum of (y - delta)^2
+    chatter: torch.Tensor                   # [4][n] float64: sum of (u_k - u_{k-1})^2 of the applied controls
+    meas: torch.Tensor                      # [8][n] float64: the last measurement
+    seed: int = 0
+    steps_accumulated: int = field(default=0)
+
+    @classmethod
+    def zeros(cls, n: int, device, seed: int = 0) -> "LqgState":
+        z = lambda rows: torch.zeros((rows, n), dtype=torch.float64, device=device)
+        return cls(z(8), z(L.FD_NU), torch.zeros(1, dtype=torch.int32, device=device), z(8), z(8), z(L.FD_NU), z(8), int(seed))
+
+    def reset(self, seed: Optional[int] = None):
+        """Back to the trim (xhat = 0, du_prev = 0), step word and accumulators to zero; optionally a new seed."""
+        for t in (self.xhat, self.du_prev, self.step, self.err_est, self.err_meas, self.chatter, self.meas):
+            t.zero_()
+        self.steps_accumulated = 0
+        if seed is not None:
+            self.seed = int(seed)
+
+
+def step_into(precision: str, x: torch.Tensor, lqr_design: Q.LqrDesign, kalman: KalmanDesign, state: LqgState, params: torch.Tensor,
+              type_index: Optional[torch.Tensor], dt: float, n_steps: int, feedback="estimate", z: Optional[torch.Tensor] = None,
+              surf_out: Optional[torch.Tensor] = None, sat_steps: Optional[torch.Tensor] = None, accumulate: bool = True):
+    """One launch of fdyn_lqg_step_<precision>: x [12][n] in the precision's storage type, advanced in place; then the step word
+    advances by n_steps (on the stream).  z: None = in-kernel draws, or [n_steps][8][n] float64 standard normals to replay."""
+    if lqr_design.x0 is None or lqr_design.u0 is None:
+        raise ValueError("the LQR design carries no trim point (x0, u0)")
+    if kalman.sigma is None:
+        raise ValueError("the Kalman design carries no measurement noise (sigma)")
+    n = int(x.shape[1])
+    if x.dtype != _lib.state_dtype(precision) or lqr_design.n != n or kalman.n != n:
+        raise ValueError(f"x must be [12][{lqr_design.n}] {_lib.state_dtype(precision)}, and both designs of that fleet")
+    fb = FEEDBACK[feedback] if isinstance(feedback, str) else int(feedback)
+    if z is not None and (tuple(z.shape) != (int(n_steps), 8, n) or z.dtype != torch.float64 or not z.is_contiguous()):
+        raise ValueError(f"z must be contiguous float64 [{int(n_steps)}][8][{n}]")
+    acc = (state.err_est, state.err_meas, state.chatter, state.meas) if accumulate else (None, None, None, None)
+    rc = getattr(_lib.load(), f"fdyn_lqg_step_{precision}")(
+        _lib.ptr(x), _lib.ptr(lqr_design.x0), _lib.ptr(lqr_design.u0), _lib.ptr(lqr_design.K), _lib.ptr(type_index), _lib.ptr(params),
+        int(params.shape[0]), n, float(dt), int(n_steps), _lib.ptr(surf_out), _lib.ptr(sat_steps), _lib.ptr(kalman.F),
+        _lib.ptr(kalman.sigma), _lib.ptr(state.xhat), _lib.ptr(state.du_prev), int(state.seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(state.step),
+        _lib.ptr(z), fb, *(_lib.ptr(t) for t in acc), _lib.current_stream())
+    _lib.check(rc, "fdyn_lqg_step")
+    if n_steps > 0:
+        state.step.add_(int(n_steps))
+        state.steps_accumulated += int(n_steps)

@@ -525,6 +525,46 @@ int fdyn_lqr_step_f32(float* x, const double* x0, const double* u0, const double
                       int n_types, int64_t n, double dt, int n_steps, float* surf_out, int32_t* sat_steps, void* stream);
 
 
+/* ---- steady-state Kalman filter and the LQG loop (csrc/kf_kernels.hip) -----------------------------------------------------
+ * fdyn_kf_design: the estimator's design, the dual of fdyn_lqr_design, one lane per aircraft, fp64.  A, B as fdyn_linearize
+ * writes them; noise [FD_NKFN] shared or (noise_per_lane != 0) [FD_NKFN][n] (FD_KFN_*).  Per block (a, b) of fdyn_lqr_design,
+ * every state measured (C = I), products summed left to right, every inverse the elimination with the 1e-14 relative pivot:
+ *   discretise  ad = a dt; T_0 = S = I, T_k = (T_k-1 ad) / (k + 1), S += T_k for k = 1..17; Phi = I + ad S, Gamma = dt (S b).
+ *               |a|_inf dt > 1.5 is BAD_INPUT: the first dropped term is then above 1e-14.
+ *   solve       V = diag sigma^2, W = diag s^2 dt: P = Phi (P - P (P + V)^-1 P) Phi^T + W by the doubling loop of fdyn_lqr_design
+ *               from A_0 = Phi^T, G_0 = V^-1, H_0 = W (same stopping rule, at most 30 steps); P = (H + H^T) / 2, L = P (P + V)^-1.
+ * Outputs: F [FD_NKF][n] (FD_KF_*), residual [n] = max|Phi (P - L P) Phi^T + W - P| / max|P| of the worse block (NaN for a
+ * BAD_INPUT lane), iters [n], status [n] int32 (FD_KF_* bits).  Status 0 is a certificate: P > 0 (L D L^T with every d > 0),
+ * W > 0 and a residual <= 1e-8 make P a Lyapunov function of Phi (I - L), which is therefore Schur.  A lane
+ * with status != 0 gets Phi = I, Gamma = 0, L = I: its estimate is the measurement.  Neither entry point synchronises or allocates. */
+int fdyn_kf_design(const double* A, const double* B, double dt, const double* noise, int noise_per_lane, int64_t n, double* F,
+                   double* residual, int32_t* iters, int32_t* status, void* stream);
+/* fdyn_lqg_step_*: the output-feedback loop in one launch, the arguments of fdyn_lqr_step_* and the physics of it to the bit.
+ * Each step s = 0, 1, ...:  d = the eight words of x - x0 as fdyn_lqr_step_* forms them;  y = d + sigma z_s;  per block in the
+ * glue type (fp64 for _f64, fp32 for _mixed and _f32): pred = Phi xhat + Gamma du_prev, xhat = pred + L (y - pred), no angle wrap
+ * of the innovation;  err_est += (xhat - d)^2, err_meas += (y - d)^2;  u = u0 - K f with f = xhat, y or d (feedback =
+ * FD_LQG_*);  chatter += (clip(u) - (u0 + du_prev))^2, sat_steps counts the clipped steps, du_prev = clip(u) - u0;  set_controls
+ * and one RK4 of dt.  F [FD_NKF][n], sigma [8] fp64; xhat [8][n] and du_prev [FD_NU][n] fp64, in and out.  z = NULL: the
+ * normals are drawn in the kernel, Philox counter (row low, row high, *step + s + 1, FD_PHX_LQG + b), block b = 0 the
+ * longitudinal four, b = 1 the lateral four, Box-Muller paired as the sensor layer pairs it (step = int32 in device memory,
+ * NULL = 0; the caller advances it by n_steps after the launch).  z [n_steps][8][n] fp64: these normals instead.  The four
+ * accumulators err_est [8][n], err_meas [8][n], chatter [FD_NU][n] (added to) and meas_out [8][n] (the last y, overwritten)
+ * are fp64 and may each be NULL.  n_steps == 0 computes the controls from the stored xhat (from d when feedback is
+ * FD_LQG_TRUTH) and changes nothing else.                                                                                      */
+int fdyn_lqg_step_f64(double* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params,
+                      int n_types, int64_t n, double dt, int n_steps, double* surf_out, int32_t* sat_steps, const double* F,
+                      const double* sigma, double* xhat, double* du_prev, uint64_t seed, const int32_t* step, const double* z,
+                      int feedback, double* err_est, double* err_meas, double* chatter, double* meas_out, void* stream);
+int fdyn_lqg_step_mixed(double* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params,
+                        int n_types, int64_t n, double dt, int n_steps, double* surf_out, int32_t* sat_steps, const double* F,
+                        const double* sigma, double* xhat, double* du_prev, uint64_t seed, const int32_t* step, const double* z,
+                        int feedback, double* err_est, double* err_meas, double* chatter, double* meas_out, void* stream);
+int fdyn_lqg_step_f32(float* x, const double* x0, const double* u0, const double* K, const uint8_t* type, const double* params,
+                      int n_types, int64_t n, double dt, int n_steps, float* surf_out, int32_t* sat_steps, const double* F,
+                      const double* sigma, double* xhat, double* du_prev, uint64_t seed, const int32_t* step, const double* z,
+                      int feedback, double* err_est, double* err_meas, double* chatter, double* meas_out, void* stream);
+
+
 /* ---- sensor layer (csrc/sensor_kernels.hip) ---------------------------------------------------------------------------
  * NoisySensorInterface.update (interfaces/sensor.py:199-243) for n aircraft: meas [FD_NMS][n] = the 12 state words +
  * airspeed + altitude with Gaussian noise, body rates additionally offset by the gyro bias; bias [FD_NSB][n]

@@ -175,10 +175,10 @@ enum {
  * layouts").  Env kernels, counter (env, episode, step, word): the IC and command record FD_PHX_RESET..+3, the random-walk command
  * increment FD_PHX_RANDOM_WALK, the randomisation rows FD_PHX_DR_RESET..+2, the initial gust FD_PHX_DR_GUST0, the gust update
  * FD_PHX_GUST.  Row kernels, counter (row low, row high, step, word): the policy's action noise FD_PHX_ACTION, the five blocks of
- * a sensor update FD_PHX_SENSOR..+4.                                                                                          */
+ * a sensor update FD_PHX_SENSOR..+4, the two blocks of an LQG step's measurement noise FD_PHX_LQG..+1.                        */
 enum {
     FD_PHX_RESET = 0, FD_PHX_RANDOM_WALK = 7, FD_PHX_DR_RESET = 16, FD_PHX_DR_GUST0 = 19, FD_PHX_GUST = 20,
-    FD_PHX_ACTION = 0x51, FD_PHX_SENSOR = 0x60
+    FD_PHX_ACTION = 0x51, FD_PHX_SENSOR = 0x60, FD_PHX_LQG = 0x70
 };
 
 /* ---- per-episode evaluation metrics, learned_controllers/eval/metrics.py:8-40 (field order of RateControlMetrics) */
@@ -268,6 +268,22 @@ enum { FD_LQK_LON = 0, FD_LQK_LAT = 8, FD_NLQK = 16 };
  *   NO_CERTIFICATE  X is not positive definite or the Riccati residual exceeds 1e-8
  *   BAD_INPUT       a word of the two blocks of A, B is not finite, or a weight is not finite and > 0: nothing was solved   */
 enum { FD_LQR_NOT_CONVERGED = 1, FD_LQR_NO_CERTIFICATE = 2, FD_LQR_BAD_INPUT = 4 };
+
+/* ---- steady-state Kalman filter and the LQG loop (fdyn_kf_design / fdyn_lqg_step_*, csrc/kf_kernels.hip) -------------- */
+/* noise [FD_NKFN] fp64: the measurement standard deviations sigma of (u, w, q, theta | v, p, r, phi), then the process-noise
+ * rates s of the same eight words, in state units per sqrt(s)                                                           */
+enum { FD_KFN_SIGMA = 0, FD_KFN_RATE = 8, FD_NKFN = 16 };
+/* filter F [FD_NKF][n] fp64, every matrix row-major: the discretised blocks Phi 4 x 4 and Gamma 4 x 2 (columns elevator,
+ * throttle | aileron, rudder) and the steady-state gains L 4 x 4                                                         */
+enum { FD_KF_PHI_LON = 0, FD_KF_PHI_LAT = 16, FD_KF_GAMMA_LON = 32, FD_KF_GAMMA_LAT = 40, FD_KF_L_LON = 48, FD_KF_L_LAT = 64, FD_NKF = 80 };
+/* status bits of a filter design; 0 = a CERTIFIED stable filter
+ *   NOT_CONVERGED   the doubling iteration hit its cap, a singular pivot or a non-finite value
+ *   NO_CERTIFICATE  P is not positive definite, P + V is singular or the residual of the filter equation exceeds 1e-8
+ *   BAD_INPUT       a word of the two blocks of A, B is not finite, a sigma or a rate is not finite and > 0, dt is outside
+ *                   (1e-6, 1] or |a|_inf dt > 1.5 (the series of the discretisation is cut where that bound holds)         */
+enum { FD_KF_NOT_CONVERGED = 1, FD_KF_NO_CERTIFICATE = 2, FD_KF_BAD_INPUT = 4 };
+/* what the LQG loop feeds back: the filter's estimate, the raw measurement, or the true state (= fdyn_lqr_step_*)         */
+enum { FD_LQG_ESTIMATE = 0, FD_LQG_MEASUREMENT = 1, FD_LQG_TRUTH = 2 };
 
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
