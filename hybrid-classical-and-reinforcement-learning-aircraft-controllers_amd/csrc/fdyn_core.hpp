@@ -115,6 +115,17 @@ FD_DEV f32x2 rotate_small(f32x2 sc, float d)
     const float sd = __builtin_fmaf(p2.y, d, d);
     return pk_fma_bx_nhi(sc, p2, sc.yx * bc(sd));
 }
+// the same rotation by d = dd.x = dd.y, for an increment that arrives as a broadcast of one half of a packed product: the
+// sine word is formed in both halves by one packed FMA (the scalar FMA, twice) instead of a scalar FMA and a copy into the
+// half the broadcast reads
+FD_DEV f32x2 rotate_small_bc(f32x2 sc, f32x2 dd)
+{
+    const float z = dd.x * dd.x;
+    const f32x2 p1 = pk_fma(bc(z), (f32x2){ 4.1666667908e-2f, 8.3333337680e-3f }, (f32x2){ -0.5f, -1.6666667163e-1f });
+    const f32x2 p2 = pk_fma(bc(z), p1, (f32x2){ 1.0f, 0.0f });
+    const f32x2 sd = pk_fma(p2.yy, dd, dd);
+    return pk_fma_bx_nhi(sc, p2, sc.yx * sd);
+}
 // cos(x): Taylor to x^8 while |x| <= 0.8 rad (truncation < 3e-8; a bank command is limited to 25 deg), full reduction beyond
 FD_DEV float cos_bounded(float x)
 {
@@ -175,6 +186,19 @@ FD_DEV f32x2 atan_asin_wide(float ta, float za, float tb, float zb)
     pb = __builtin_fmaf(zb, pb, 2.6334178448e-01f);
     pb = __builtin_fmaf(zb, pb, -7.6388612390e-02f);
     const f32x2 z = { za, zb }, t = { ta, tb };
+    f32x2 p = pk_fma(z, (f32x2){ pa, pb }, (f32x2){ 1.0221967846e-01f, 5.3024884313e-02f });
+    p = pk_fma(z, p, (f32x2){ -1.4136675000e-01f, 4.1755288839e-02f });
+    p = pk_fma(z, p, (f32x2){ 1.9987617433e-01f, 7.5183674693e-02f });
+    p = pk_fma(z, p, (f32x2){ -3.3332955837e-01f, 1.6666238010e-01f });
+    return pk_fma(p * z, t, t);
+}
+// the same from operands that already are the pairs t = (ta, tb), z = (za, zb)
+FD_DEV f32x2 atan_asin_wide(f32x2 t, f32x2 z)
+{
+    const float pa = __builtin_fmaf(z.x, 2.0541535690e-02f, -6.1546623707e-02f);
+    float pb = __builtin_fmaf(z.y, 2.1202674508e-01f, -3.1944271922e-01f);
+    pb = __builtin_fmaf(z.y, pb, 2.6334178448e-01f);
+    pb = __builtin_fmaf(z.y, pb, -7.6388612390e-02f);
     f32x2 p = pk_fma(z, (f32x2){ pa, pb }, (f32x2){ 1.0221967846e-01f, 5.3024884313e-02f });
     p = pk_fma(z, p, (f32x2){ -1.4136675000e-01f, 4.1755288839e-02f });
     p = pk_fma(z, p, (f32x2){ 1.9987617433e-01f, 7.5183674693e-02f });
@@ -380,6 +404,33 @@ template <typename T> struct Params {
             }
         }
     }
+    // Upper bound of every Euler-angle increment the fp32 integrator (rk4_fast_step, STRAIGHT) feeds to rotate_small during a
+    // sub-step of `h` seconds, for one type (src = its FD_P_* block), in fp64.
+    //   rates:  the stored body rates are clamped to R = max_rate after every sub-step, and the stage states are x0 + h_s k with
+    //           |k| <= A = max_ang_acc, h_s = h/2, h/2, h: the four evaluations see |p|,|q|,|r| <= R, R + hA/2, R + hA/2, R + hA;
+    //   Euler:  |theta'| = |cphi q - sphi r| <= sqrt2 Ri,  |psi'| = |sphi q + cphi r| / cos(th_e) <= sqrt2 Ri / cos(max_pitch),
+    //           |phi'| = |p + tan(th_e) (sphi q + cphi r)| <= Ri (1 + sqrt2 tan(max_pitch)) -- th_e is the pitch clamped to
+    //           +-max_pitch (dynamics_fast takes the staged sin / cos of the limit beyond it) -- so every rate is <= G Ri with
+    //           G = max(1 + sqrt2 tan(max_pitch), sqrt2 / cos(max_pitch));
+    //   stage increments: (h/2) G R, (h/2) G (R + hA/2), h G (R + hA/2);
+    //   final increment:  (h/6) G (R + 2 (R + hA/2) + 2 (R + hA/2) + R + hA) = h G (R + hA/2) -- the weighted mean of the stage
+    //           bounds, not the worst stage (the default airframe at h = 1 ms: 0.1164 against 0.1250 for the worst stage).
+    // SLACK covers the fp32 evaluation: each rate is a handful of fp32 operations (2^-24 relative each, the reciprocal of the
+    // cosine 2^-22), and the carried sin / cos drift from those of the stored angle by the rotation series' truncation
+    // (d^5 / 120 <= 2.6e-7 per rotation, at most 80 rotations a launch: 2e-5 absolute, 2.4e-4 of cos(85 deg)).
+    // NaN: a finite state gives finite increments (every divisor is clamped away from 0, dynamics_fast's header), the bound
+    // then holds, and the state is re-checked after every sub-step by rk4_fast_step's combined predicate, as before; a
+    // non-finite limit or step fails the comparison below (written so that a NaN fails it) and keeps the general form.
+    static FD_DEV double euler_increment_bound(const double* __restrict__ src, double h)
+    {
+        constexpr double SLACK = 1.0 + 1.0 / 512.0;
+        const double R = src[FD_P_MAX_RATE_RAD], A = src[FD_P_MAX_ANGULAR_ACCELERATION], mp = src[FD_P_MAX_PITCH_RAD];
+        if (!(R >= 0.0 && A >= 0.0 && h > 0.0 && mp >= 0.0 && mp <= 1.5)) return 1.0e300;
+        const double rt2 = 1.4142135623730951;
+        const double G = fmax(1.0 + rt2 * tan(mp), rt2 / cos(mp));
+        return SLACK * h * G * (R + 0.5 * h * A);
+    }
+    static FD_DEV bool small_steps_ok(const double* __restrict__ src, double h) { return euler_increment_bound(src, h) <= 0.125; }
 };
 
 // limits applied to the stored state after each RK4 step (in the storage type)
@@ -584,6 +635,14 @@ FD_DEV float trig_rotate_scaled(const Trig& t0, float h, float kphi, float kth, 
     return trig_rotate(t0, d2.x, d2.y, h * kpsi, t);
 }
 
+// block-free sub-step loop: rotate by the pair (d_phi, d_theta) and by d_psi = dpsi.x; no maximum (nothing tests it there)
+FD_DEV void trig_rotate_pairs(const Trig& t0, fast::f32x2 d2, fast::f32x2 dpsi, Trig& t)
+{
+    t.phi = fast::rotate_small_bc(t0.phi, d2.xx);
+    t.th = fast::rotate_small_bc(t0.th, d2.yy);
+    t.psi = fast::rotate_small_bc(t0.psi, dpsi.xx);
+}
+
 #define FD_UNLIKELY(c) __builtin_expect(!!(c), 0)
 #ifdef FD_PHASE_STAMPS
 // timing experiment only: how often wave 0 of a workgroup enters the rare blocks ([0] wave entries, [1] lane entries of the
@@ -607,10 +666,14 @@ __device__ unsigned fdyn_dbg_cnt[4096 * 8];
 // envs 2.41e9 env-steps/s against 2.25e9 with the straight form.  The arithmetic is the same expression for expression: the
 // two forms are bit-equal (tests/test_gpu_parity_scale.py compares the two env builds).
 // WIND: as dynamics<double>; R^T W comes from the carried trigonometry (rebuilt first when it is stale), 15 VALU.
-template <bool STRAIGHT = true, bool WIND = false>
+// RARE = false (STRAIGHT, no wind): the caller has established that neither condition of the rare block below can hold during
+// this launch (small_steps_ok: no type needs atan2 and no Euler-angle increment can exceed 0.125 rad) -- the evaluation then
+// has no rare block and no dmax test, it is one basic block, and `tg` is read only.
+template <bool STRAIGHT = true, bool WIND = false, bool RARE = true>
 FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, const float (&x)[FD_NX], Trig& tg, float dmax,
                           float (&xd)[FD_NX], const Wind<float>& wnd = Wind<float>{})
 {
+    static_assert(RARE || (STRAIGHT && !WIND), "the block-free form exists for the straight, still-air evaluation only");
     const float ug = x[3], vg = x[4], wg = x[5], theta = x[7];
     const float p = x[9], q = x[10], r = x[11];
     float u = ug, v = vg, w = wg;
@@ -637,9 +700,18 @@ FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, cons
     const float au_min = fast::max_nc(au, P.min_u);
     const float us = au > 1e-6f ? __builtin_copysignf(au_min, u) : P.min_u;
     const float inv_h = fast::rsq(__builtin_fmaf(us, us, vw_sq.y));                         // |u_safe| >= min_u > 0
-    const fast::f32x2 xt_ab = vw * (fast::f32x2){ inv_V, fast::rcp(us) };                   // v / V, w / u_safe
+    // RARE: (v / V, w / u_safe).  Block-free form: (w / u_safe, v / V) -- the same two products, in the order the polynomial
+    // pair below reads them, (alpha word, beta word), so that its operands are these registers and not copies of their halves
+    constexpr int IA = RARE ? 1 : 0, IB = 1 - IA;           // halves of xt_ab / xt_sq that hold the alpha and the beta word
+    fast::f32x2 xt_ab, rcps = { 0.0f, 0.0f };
+    if constexpr (RARE) xt_ab = vw * (fast::f32x2){ inv_V, fast::rcp(us) };
+    else {
+        rcps = (fast::f32x2){ fast::rcp(us), inv_V };
+        asm("" : "+v"(rcps));                               // one 64-bit value: 1 / V is broadcast from its half below
+        xt_ab = vw.yx * rcps;
+    }
     const fast::f32x2 xt_sq = xt_ab * xt_ab;
-    const float t_alpha = xt_ab.y;
+    const float t_alpha = xt_ab[IA];
     const bool a_in = __builtin_fabsf(w) <= P.tan_alpha_fast * us;
     const float sin_alpha = a_in ? w * inv_h : __builtin_copysignf(P.sin_max_alpha, w);
     const float cos_alpha = a_in ? us * inv_h : P.cos_max_alpha;
@@ -653,7 +725,7 @@ FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, cons
     // step (113 k cycles for the RK4 phase against 72 k, scratch/phase_stamps.py) and the launch waited for those waves.
     const float av = __builtin_fabsf(v);
     const bool b_in = av <= FD_ASIN_WIDE_LIMIT * Vs;
-    const float xb = xt_ab.x;
+    const float xb = xt_ab[IB];
     auto beta_tail = [&]() {                                 // |v| / V beyond 0.75
         const float vv_rest = airspeed >= P.min_airspeed ? uw2 : __builtin_fmaxf(__builtin_fmaf(Vs, Vs, -(v * v)), 0.0f);   // V^2 - v^2 (V clamped: :364)
         const float half_om = 0.5f * (vv_rest * fast::rcp(Vs * (Vs + av)));                 // (1 - |v| / V) / 2 <= 0.125
@@ -667,12 +739,20 @@ FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, cons
         const float vv_rest = airspeed >= P.min_airspeed ? uw2 : __builtin_fmaxf(__builtin_fmaf(Vs, Vs, -vw_sq.x), 0.0f);
         const float half_om = 0.5f * (vv_rest * fast::rcp(Vs * (Vs + av)));
         b_t = b_in ? xb : fast::sqrt(half_om);
-        z_b = b_in ? xt_sq.x : half_om;
+        z_b = b_in ? xt_sq[IB] : half_om;
     } else {
-        b_t = xb; z_b = xt_sq.x;                            // the tail is fixed up in the rare block below
+        b_t = xb; z_b = xt_sq[IB];                          // the tail is fixed up in the rare block below
     }
-    const fast::f32x2 ab = fast::atan_asin_wide(t_alpha, xt_sq.y, b_t, z_b);
-    const float alpha_poly = fast::pinned(ab.x);
+    fast::f32x2 ab;
+    if constexpr (RARE) {
+        ab = fast::atan_asin_wide(t_alpha, xt_sq[IA], b_t, z_b);
+    } else {
+        fast::f32x2 t2 = xt_ab, z2 = xt_sq;                 // the beta halves replaced in place
+        t2.y = b_t; z2.y = z_b;
+        ab = fast::atan_asin_wide(t2, z2);
+    }
+    float alpha_poly = ab.x;
+    if constexpr (RARE) alpha_poly = fast::pinned(ab.x);   // (the block-free form has no branch to if-convert against)
     const float alpha = a_in ? alpha_poly : __builtin_copysignf(P.max_alpha, w);
     if constexpr (STRAIGHT) beta = b_in ? ab.y : __builtin_copysignf(__builtin_fmaf(-2.0f, ab.y, 1.5707963267948966f), v);
     else beta = ab.y;
@@ -684,7 +764,7 @@ FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, cons
 
     // ---- the rare block: an Euler-angle increment too large for the rotation series (after a wrap / pitch clamp, or 10 ms steps
     // of a tumbling aircraft), or an aircraft type whose alpha limit lies beyond the polynomial -- transient or absent
-    const bool ordinary = (dmax <= 0.125f) & (P.alpha_needs_atan2 == 0.0f) & (STRAIGHT | b_in);
+    const bool ordinary = RARE ? (dmax <= 0.125f) & (P.alpha_needs_atan2 == 0.0f) & (STRAIGHT | b_in) : true;
     float alpha_r = alpha, sin_alpha_r = sin_alpha, cos_alpha_r = cos_alpha;
     if (FD_UNLIKELY(!ordinary)) {
         FD_DBG_COUNT(0)
@@ -718,18 +798,33 @@ FD_DEV void dynamics_fast(const Params<float>& P, const Controls<float>& C, cons
     const float thrust = C.thrust_max * __builtin_fmaxf(0.0f, __builtin_fmaf(-airspeed, P.inv_thrust_zero_v, 1.0f));   // :403
 
     // :409-411 + :455-460   a = F/m + g-terms - omega x v
-    const f32x2 g_cs = bc(P.g) * (tg.phi * bc(cth));                                        // g (cth sphi), g (cth cphi)
+    f32x2 g_cs;
+    if constexpr (RARE) g_cs = bc(P.g) * (tg.phi * bc(cth));
+    else g_cs = bc(P.g) * (tg.phi * tg.th.yy);                                        // g (cth sphi), g (cth cphi)
     xd[3] = __builtin_fmaf(fxz.x + thrust, P.inv_mass, __builtin_fmaf(r, vg, __builtin_fmaf(-q, wg, -(P.g * sth))));
     xd[4] = __builtin_fmaf(q_S * C.cy, P.inv_mass, __builtin_fmaf(p, wg, __builtin_fmaf(-r, ug, g_cs.x)));
     xd[5] = __builtin_fmaf(-fxz.y, P.inv_mass, __builtin_fmaf(q, ug, __builtin_fmaf(-p, vg, g_cs.y)));
 
     // :416-431, :474-482  roll and yaw moments have one shape: packed as (l, n)
-    const f32x2 hV = P.pk_half_b_c * bc(inv_V);                             // :416-417
+    f32x2 hV;                                                               // :416-417
+    if constexpr (RARE) hV = P.pk_half_b_c * bc(inv_V);
+    else hV = P.pk_half_b_c * rcps.yy;
     const f32x2 qSbc = bc(q_S) * P.pk_b_c;
-    const f32x2 pr = { p, r };
-    const f32x2 ln_in = fast::pk_fma(P.pk_damp_pr * pr, bc(hV.x), C.pk_da_dr);
+    f32x2 ln_in;
+    float damp_q = 0.0f;
+    if constexpr (RARE) {
+        const f32x2 pr = { p, r };
+        ln_in = fast::pk_fma(P.pk_damp_pr * pr, bc(hV.x), C.pk_da_dr);
+    } else {
+        // (p, r) are the high halves of two different state pairs; (q, r) is a pair: its damping products come packed (the
+        // pitch one with them), and the two FMAs write the halves of ln_in -- the same products and FMAs, no gathering copies
+        const f32x2 d_qr = (f32x2){ P.damp_pitch, P.pk_damp_pr.y } * (f32x2){ q, r };
+        ln_in = (f32x2){ __builtin_fmaf(P.pk_damp_pr.x * p, hV.x, C.pk_da_dr.x), __builtin_fmaf(d_qr.y, hV.x, C.pk_da_dr.y) };
+        damp_q = d_qr.x;
+    }
     const f32x2 ln = bc(qSbc.x) * fast::pk_fma(P.pk_beta_ln, bc(beta), ln_in);
-    const float m_moment = qSbc.y * __builtin_fmaf(P.cm_alpha, alpha_r, __builtin_fmaf(P.damp_pitch * q, hV.y, C.cm_de));
+    if constexpr (RARE) damp_q = P.damp_pitch * q;
+    const float m_moment = qSbc.y * __builtin_fmaf(P.cm_alpha, alpha_r, __builtin_fmaf(damp_q, hV.y, C.cm_de));
     const f32x2 gy = { __builtin_fmaf(-P.izz_m_iyy * q, r, ln.x), __builtin_fmaf(-P.iyy_m_ixx * p, q, ln.y) };
     const f32x2 a_pr = gy * P.pk_inv_i_pr;                                // :474-482
     xd[9] = a_pr.x;
@@ -807,10 +902,14 @@ FD_DEV void post_step(const Limits<S>& Lm, S (&x)[FD_NX])
 // ----- the fp32-evaluation integrator state: fp32 copy of the stored state + carried trigonometry -------------------
 // Lives in registers across the sub-steps of a launch AND across the control steps of the cascade kernels, whose glue
 // (derived scalars, guidance) reads the same fp32 copy and the same sin / cos.
+struct PredLits { float pi, inf, zero; };   // literals of rk4_fast_step's predicate (a caller may hold them in registers)
 struct FastRK {
     float x0[FD_NX];        // fp32 copy of the stored state
     Trig t0;                // sin / cos of x0[6..8], rotated incrementally
     float d0;               // max |increment| t0 was last rotated by (> 0.125: the next user rebuilds it in full)
+    // rk4_fast_step<.., RARE = false> only: x0 as the pairs (x0[2j], x0[2j+1]), carried instead of x0, and its predicate's literals
+    fast::f32x2 xp[FD_NX / 2];
+    PredLits lit;
     template <typename S> FD_DEV void init(const S (&x)[FD_NX])
     {
 #pragma unroll
@@ -828,11 +927,21 @@ struct FastRK {
 // the state; the storage type S sees ONE add per word per step (x += S(dt/6 * sum)) -- that add is what keeps the "mixed"
 // variant inside the 1e-4 gate.  The clamps / wraps of :256-291 are tested on the fp32 copy with one combined predicate and
 // the (rare) fix-up runs under a wave-level branch.
-template <typename S, bool STRAIGHT = true, bool WIND = false>
+template <typename S, bool STRAIGHT = true, bool WIND = false, bool RARE = true>
 FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Controls<float>& C, S (&x)[FD_NX], FastRK& f,
                           float hdt, float fdt, float dt6, const Wind<float>& wnd = Wind<float>{})
 {
     using T = float;
+    // RARE = false: the fp32 copy is carried from sub-step to sub-step as pairs (f.xp), the form the stage combinations and the
+    // packed operands of dynamics_fast read it in; x0 is their halves for the length of this step
+    if constexpr (!RARE) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            fast::f32x2 v = f.xp[j];
+            asm("" : "+v"(v));                                  // one 64-bit value from here on: its halves are read in place
+            f.x0[2 * j] = v.x; f.x0[2 * j + 1] = v.y;
+        }
+    }
     // position (0..2) feeds nothing back, and roll / yaw enter only through their sin / cos: the stage states carry velocity,
     // angles (for the rare full rebuild and the +-85 deg guard) and rates; the trigonometry is rotated
     T xt[FD_NX], k[FD_NX];
@@ -857,16 +966,24 @@ FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Con
             }
         }
     };
-    dynamics_fast<STRAIGHT, WIND>(P, C, f.x0, f.t0, f.d0, k, wnd);                            // k1
+    dynamics_fast<STRAIGHT, WIND, RARE>(P, C, f.x0, f.t0, f.d0, k, wnd);                            // k1
     stage(hdt, T(1), true);
-    T dm = trig_rotate_scaled(f.t0, hdt, k[6], k[7], k[8], tt);
-    dynamics_fast<STRAIGHT, WIND>(P, C, xt, tt, dm, k, wnd);                        // k2
+    // RARE = false: the increments as halves of the packed products h (k6, k7), h (k8, k9) -- the products the scalar form makes
+    auto rotate_stage = [&](T h) {
+        trig_rotate_pairs(f.t0, fast::bc(h) * (f32x2){ k[6], k[7] }, fast::bc(h) * (f32x2){ k[8], k[9] }, tt);
+    };
+    T dm = T(0);
+    if constexpr (RARE) dm = trig_rotate_scaled(f.t0, hdt, k[6], k[7], k[8], tt);
+    else rotate_stage(hdt);
+    dynamics_fast<STRAIGHT, WIND, RARE>(P, C, xt, tt, dm, k, wnd);                        // k2
     stage(hdt, T(2), false);
-    dm = trig_rotate_scaled(f.t0, hdt, k[6], k[7], k[8], tt);
-    dynamics_fast<STRAIGHT, WIND>(P, C, xt, tt, dm, k, wnd);                        // k3
+    if constexpr (RARE) dm = trig_rotate_scaled(f.t0, hdt, k[6], k[7], k[8], tt);
+    else rotate_stage(hdt);
+    dynamics_fast<STRAIGHT, WIND, RARE>(P, C, xt, tt, dm, k, wnd);                        // k3
     stage(fdt, T(2), false);
-    dm = trig_rotate_scaled(f.t0, fdt, k[6], k[7], k[8], tt);
-    dynamics_fast<STRAIGHT, WIND>(P, C, xt, tt, dm, k, wnd);                        // k4
+    if constexpr (RARE) dm = trig_rotate_scaled(f.t0, fdt, k[6], k[7], k[8], tt);
+    else rotate_stage(fdt);
+    dynamics_fast<STRAIGHT, WIND, RARE>(P, C, xt, tt, dm, k, wnd);                        // k4
     T ksum[FD_NX], inc[FD_NX];
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
@@ -886,7 +1003,8 @@ FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Con
         if (STRAIGHT && i >= 9) x[i] = M<S>::abs(x[i]) > Lm.max_rate ? M<S>::copysign(Lm.max_rate, x[i]) : x[i];
         f.x0[i] = T(x[i]);
     }
-    f.d0 = trig_rotate(f.t0, inc[6], inc[7], inc[8], f.t0);
+    if constexpr (RARE) f.d0 = trig_rotate(f.t0, inc[6], inc[7], inc[8], f.t0);
+    else trig_rotate_pairs(f.t0, (f32x2){ inc[6], inc[7] }, (f32x2){ inc[8], inc[9] }, f.t0);
     // one predicate for every clamp / wrap / guard of :256-291, evaluated on the fp32 copy
     f32x2 sum2 = { f.x0[0], f.x0[1] };                   // all finite <=> the sum is finite: only its finiteness is read
 #pragma unroll
@@ -901,13 +1019,17 @@ FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Con
     // sincos rebuild behind one predicate that included the rate clamp: a wave holding one aircraft at that clamp ran 20
     // fix-ups + 19 rebuilds per env step, 100-111 k cycles for the RK4 phase against 71.6 k for an undisturbed wave --
     // scratch/phase_stamps.py, shader-clock stamps -- and the launch waited for it.)
-    bool lim = !(vmax <= T(Lm.max_vel)) | (f.x0[2] > T(0)) | !(amax <= T(FD_PI));
+    bool lim;
+    if constexpr (RARE) lim = !(vmax <= T(Lm.max_vel)) | (f.x0[2] > T(0)) | !(amax <= T(FD_PI));
+    else lim = !(vmax <= T(Lm.max_vel)) | (f.x0[2] > f.lit.zero) | !(amax <= f.lit.pi);
     if constexpr (!STRAIGHT) {
         // the same comparison the straight form makes, in the storage type (an fp32 copy can sit exactly on the limit while
         // the stored value is a rounding beyond it)
         lim |= (M<S>::abs(x[9]) > Lm.max_rate) | (M<S>::abs(x[10]) > Lm.max_rate) | (M<S>::abs(x[11]) > Lm.max_rate);
     }
-    const bool ang = !(__builtin_fabsf(f.x0[7]) <= T(Lm.max_pitch)) | !M<T>::finite(sum);
+    bool ang;
+    if constexpr (RARE) ang = !(__builtin_fabsf(f.x0[7]) <= T(Lm.max_pitch)) | !M<T>::finite(sum);
+    else ang = !(__builtin_fabsf(f.x0[7]) <= T(Lm.max_pitch)) | !(__builtin_fabsf(sum) < f.lit.inf);
     if (FD_UNLIKELY(lim | ang)) {
         FD_DBG_COUNT(2)
 #ifdef FD_PHASE_STAMPS
@@ -918,7 +1040,14 @@ FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Con
             post_step<S, T>(Lm, x);
 #pragma unroll
             for (int i = 0; i < 12; ++i) f.x0[i] = T(x[i]);
-            f.d0 = T(1);                                         // the next user rebuilds the trigonometry in full
+            if constexpr (RARE) {
+                f.d0 = T(1);                                     // the next user rebuilds the trigonometry in full
+            } else {
+                // no evaluation tests d0 in this form: rebuild here, from the refreshed copy -- the inputs the next k1 would
+                // have rebuilt from, so the same bits
+                f.t0 = trig_of(f.x0[6], f.x0[7], f.x0[8]);
+                f.d0 = T(0);
+            }
         } else {
 #pragma unroll
             for (int i = 3; i < 6; ++i) x[i] = clipv(x[i], -Lm.max_vel, Lm.max_vel);          // :262
@@ -940,12 +1069,16 @@ FD_DEV void rk4_fast_step(const Params<float>& P, const Limits<S>& Lm, const Con
             for (int i = 3; i < 6; ++i) f.x0[i] = T(x[i]);
         }
     }
+    if constexpr (!RARE) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) f.xp[j] = (f32x2){ f.x0[2 * j], f.x0[2 * j + 1] };
+    }
 }
 
 // ----- Simplified6DOF.step x n_sub: RK4 + post-clamps, simplified_6dof.py:247-291 ------------------------
 // fp64 evaluation (T = double): the reference's operation order, every clamp applied every step.
 // fp32 evaluation (T = float): rk4_fast_step above.
-template <typename S, typename T, bool STRAIGHT = true, bool WIND = false>
+template <typename S, typename T, bool STRAIGHT = true, bool WIND = false, bool RARE = true>
 FD_DEV void rk4_substeps(const Params<T>& P, const Limits<S>& Lm, const Controls<T>& C, S (&x)[FD_NX], S dt, int n_sub,
                          const Wind<T>& wnd = Wind<T>{})
 {
@@ -975,7 +1108,17 @@ FD_DEV void rk4_substeps(const Params<T>& P, const Limits<S>& Lm, const Controls
         FastRK f;
         f.init(x);                                               // the ONLY full sincos of the launch (rare blocks aside)
         const T hdt = T(S(0.5) * dt), fdt = T(dt), dt6 = T(dt / S(6));
-        for (int s = 0; s < n_sub; ++s) rk4_fast_step<S, STRAIGHT, WIND>(P, Lm, C, x, f, hdt, fdt, dt6, wnd);
+        if constexpr (RARE) {
+            for (int s = 0; s < n_sub; ++s) rk4_fast_step<S, STRAIGHT, WIND, RARE>(P, Lm, C, x, f, hdt, fdt, dt6, wnd);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) f.xp[j] = (fast::f32x2){ f.x0[2 * j], f.x0[2 * j + 1] };
+            // the predicate's literals, held in scalar registers over the loop (left as literals they are materialised again in
+            // every sub-step: the comparisons that read them take no literal operand)
+            f.lit = PredLits{ float(FD_PI), __builtin_inff(), 0.0f };
+            asm volatile("" : "+s"(f.lit.pi), "+s"(f.lit.inf), "+s"(f.lit.zero));
+            for (int s = 0; s < n_sub; ++s) rk4_fast_step<S, STRAIGHT, WIND, RARE>(P, Lm, C, x, f, hdt, fdt, dt6, wnd);
+        }
     }
 }
 

@@ -978,6 +978,11 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
     EnvConsts<S> ec;
     load_env_consts<S, PREP>(EC, ec);
     const bool uses_sched = ec.cmd_type == FD_CMD_RAMP || ec.cmd_type == FD_CMD_SINE;
+    // the benched build (mixed precision, one wave per SIMD, prepared image, still air) holds the sub-step loop twice: the general
+    // one and the one without dynamics_fast's rare block, chosen per wave from the image's FD_ECD_SMALL_STEPS word
+    constexpr bool TWO_LOOPS = PREP && !OCC2 && !DR && sizeof(S) == 8 && sizeof(T) == 4;
+    bool small_steps = false;
+    if constexpr (TWO_LOOPS) small_steps = EC[FD_ECD_SMALL_STEPS] != 0.0;
     // actions == null: the fused rate-PID demonstrator drives the env.  residual_scale > 0 (with actions AND pid state):
     // ResidualRateControlEnv -- action = clip(PID + scale * residual) (residual_rate_env.py:99-157).
     const bool residual_mode = actions != nullptr && residual_scale > 0.0f && pid_state != nullptr;
@@ -1101,7 +1106,18 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
 #endif
         FD_STAMP(1)
         if constexpr (DR) rk4_substeps<S, T, !OCC2, true>(P, Lm, C, x, dt_sub, ec.n_sub, Wind<T>{ T(wair[0]), T(wair[1]), T(wair[2]) });
-        else rk4_substeps<S, T, !OCC2>(P, Lm, C, x, dt_sub, ec.n_sub);
+        else if constexpr (TWO_LOOPS) {
+            // The image says that no sub-step of this launch can move an Euler angle by more than 0.125 rad and that no type
+            // needs atan2 (Params::euler_increment_bound) -- for states inside the limits every sub-step leaves behind.  A state
+            // written from outside need not be: the wave checks the words the bound rests on once, here, and a wave holding such a
+            // state (or a non-finite angle) takes the general loop.  Both loops compute the same bits.
+            const float r_max = float(Lm.max_rate), p_max = float(Lm.max_pitch);
+            const bool outside = !(__builtin_fabsf(float(x[9])) <= r_max) | !(__builtin_fabsf(float(x[10])) <= r_max) |
+                                 !(__builtin_fabsf(float(x[11])) <= r_max) | !(__builtin_fabsf(float(x[7])) <= p_max) |
+                                 !(__builtin_fabsf(float(x[6])) < __builtin_inff()) | !(__builtin_fabsf(float(x[8])) < __builtin_inff());
+            if (small_steps && __ballot(outside) == 0ull) rk4_substeps<S, T, true, false, false>(P, Lm, C, x, dt_sub, ec.n_sub);
+            else rk4_substeps<S, T, true>(P, Lm, C, x, dt_sub, ec.n_sub);
+        } else rk4_substeps<S, T, !OCC2>(P, Lm, C, x, dt_sub, ec.n_sub);
         FD_STAMP(2)
         if constexpr (sizeof(E) == sizeof(S)) e.time += E(ec.dt);                 // :241-242 (the reference's accumulated sum)
         else e.time = E(S(step + 1) * ec.dt);                                     // fp32 env words: exact product, not an fp32 running sum
@@ -1271,7 +1287,8 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
 // constants alone, computed ONCE by the device functions the kernel itself uses (so every word is the one it would compute) --
 // the staged parameter blocks with their derived words and the env constants with the sub-step and settle-step counts.  One
 // workgroup.  FAST = the fp32-evaluation variants' derived words (Params::derive_lane_from).
-static_assert(FD_NIMG == FD_IMG_PARAMS + FD_MAX_TYPES * FD_NP_STAGED && FD_ECD_INTS + 2 <= FD_IMG_PARAMS, "fdyn_layout.h: image sections");
+static_assert(FD_NIMG == FD_IMG_PARAMS + FD_MAX_TYPES * FD_NP_STAGED && FD_ECD_INTS + 2 <= FD_ECD_SMALL_STEPS &&
+              FD_ECD_SMALL_STEPS < FD_IMG_PARAMS, "fdyn_layout.h: image sections");
 template <bool FAST>
 __global__ void __launch_bounds__(FD_BLOCK)
 rate_env_image_kernel(const double* __restrict__ params, int n_types, const double* __restrict__ EC, double* __restrict__ image)
@@ -1281,7 +1298,7 @@ rate_env_image_kernel(const double* __restrict__ params, int n_types, const doub
         const int t = i / FD_NP_STAGED, k = i - t * FD_NP_STAGED;
         blocks[i] = (t < n_types && k < FD_NP_USED) ? params[t * FD_NP + k] : 0.0;
     }
-    for (int k = threadIdx.x; k < FD_IMG_PARAMS; k += blockDim.x) if (k < FD_ECD_INTS || k >= FD_ECD_INTS + 2) image[FD_IMG_EC + k] = k < FD_NEC ? EC[k] : 0.0;
+    for (int k = threadIdx.x; k < FD_IMG_PARAMS; k += blockDim.x) if ((k < FD_ECD_INTS || k >= FD_ECD_INTS + 2) && k != FD_ECD_SMALL_STEPS) image[FD_IMG_EC + k] = k < FD_NEC ? EC[k] : 0.0;
     __syncthreads();                                               // the derived words below land on the zeros above
     constexpr int NDL = Params<double>::FD_ND_LANES;
     if (int(threadIdx.x) < n_types * NDL) {
@@ -1293,6 +1310,21 @@ rate_env_image_kernel(const double* __restrict__ params, int n_types, const doub
         load_env_consts<double>(EC, ec);
         int32_t* ic = reinterpret_cast<int32_t*>(image + FD_IMG_EC + FD_ECD_INTS);
         ic[0] = ec.max_steps; ic[1] = ec.cmd_type; ic[2] = ec.n_sub; ic[3] = ec.settle_steps;
+        // FD_ECD_SMALL_STEPS: the step kernel may run the sub-step loop without dynamics_fast's rare block (the alpha test is
+        // derive lane 5's, on the same fp32 sin / cos)
+        bool small = FAST;
+        if constexpr (FAST) {
+            const double dt_sub = ec.dt / double(ec.n_sub);
+            for (int t = 0; t < n_types; ++t) {
+                const double* src = params + t * FD_NP;
+                const double a = src[FD_P_MAX_ALPHA_RAD];
+                float snf, csf;
+                fast::sincos(float(a), snf, csf);
+                const bool poly_ok = a > 0.0 && a < 1.5 && double(snf) / double(csf) <= double(FD_ATAN_WIDE_LIMIT);
+                small = small && poly_ok && Params<double>::small_steps_ok(src, dt_sub);
+            }
+        }
+        image[FD_IMG_EC + FD_ECD_SMALL_STEPS] = small ? 1.0 : 0.0;
     }
 }
 

@@ -122,10 +122,12 @@ enum {
 /* prepared launch image of the rate env (fdyn_rate_env_image, read by fdyn_rate_env_step_img_* / _dr_img_*), fp64 words: what
  * the step derives from env_consts and the parameter table alone, computed once instead of by every wave of every launch.
  *   [FD_IMG_EC ..]     the FD_NEC env constants, then the derived counts: RK4 sub-steps per env step (fdyn_num_substeps) and the
- *                      number of consecutive settled steps at which the settling bonus starts
+ *                      number of consecutive settled steps at which the settling bonus starts, then FD_ECD_SMALL_STEPS: 1.0 when,
+ *                      for every type of the table, no Euler angle can move by more than 0.125 rad within one RK4 sub-step of
+ *                      these env constants and the alpha limit lies inside the polynomial (fp32 evaluation only, else 0.0)
  *   [FD_IMG_PARAMS ..] FD_MAX_TYPES staged parameter blocks of FD_NP_STAGED words (FD_P_* then FD_PD_*)                     */
 enum {
-    FD_ECD_INTS = FD_NEC,
+    FD_ECD_INTS = FD_NEC, FD_ECD_SMALL_STEPS = FD_NEC + 2,
     FD_IMG_EC = 0, FD_IMG_PARAMS = 16,
     FD_NIMG = FD_IMG_PARAMS + 8 * FD_NP_STAGED
 };
