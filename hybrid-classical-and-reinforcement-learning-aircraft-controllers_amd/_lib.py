@@ -91,6 +91,7 @@ SIGNATURES = {
     "fdyn_lqr_step_f64": (_i, _LQR_STEP), "fdyn_lqr_step_mixed": (_i, _LQR_STEP), "fdyn_lqr_step_f32": (_i, _LQR_STEP),
     "fdyn_kf_design": (_i, [_p, _p, _d, _p, _i, _i64, _p, _p, _p, _p, _p]),
     "fdyn_lqg_step_f64": (_i, _LQG_STEP), "fdyn_lqg_step_mixed": (_i, _LQG_STEP), "fdyn_lqg_step_f32": (_i, _LQG_STEP),
+    "fdyn_loop_margins": (_i, [_p, _p, _i, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -164,6 +164,20 @@ class BatchedSixDOF:
                     self.u, self.lqr_saturated_steps)
         self.time += kalman.dt * n_steps
 
+    # Loop margins (hcrl_amd.margins): how robust the loop step_lqr / step_lqg fly is, sampled at dt and through the estimator
+    def loop_margins(self, feedback: str = "estimate", omega=None, curve: bool = False):
+        """LoopMargins of every aircraft's loop as `step_lqg(feedback=...)` flies it, at the filter's dt: alpha_s [2][N] (the
+        smallest singular value of the return difference at the plant input, longitudinal | lateral), status 0 = the gain /
+        phase disk it stands for is guaranteed.  Needs design_lqr() and design_kalman() first.  omega: None = 64 points,
+        logarithmic from 0.01 rad/s to the Nyquist rate.  The fleet's state is not touched."""
+        from . import margins as M
+        lqr_design, kalman = getattr(self, "_lqr", None), getattr(self, "_kalman", None)
+        if lqr_design is None or kalman is None:
+            missing = "design_lqr()" if lqr_design is None else "design_kalman(dt)"
+            raise ValueError(f"{type(self).__name__}.loop_margins: {self.n} of {self.n} aircraft have no certified "
+                             f"{'stabilising gain' if lqr_design is None else 'stable filter'} (call .{missing} first)")
+        return M.loop_margins(lqr_design, kalman, feedback, omega, curve)
+
 
 class BatchedCascade(BatchedSixDOF):
     """N aircraft each flying the same waypoint mission under the 5-level cascaded PID stack."""

@@ -565,6 +565,29 @@ int fdyn_lqg_step_f32(float* x, const double* x0, const double* u0, const double
                       int feedback, double* err_est, double* err_meas, double* chatter, double* meas_out, void* stream);
 
 
+/* ---- loop margins (csrc/margin_kernels.hip) ---------------------------------------------------------------------------------
+ * fdyn_loop_margins: how much robustness the loop has as fdyn_lqr_step_* / fdyn_lqg_step_* fly it -- sampled at dt, through the
+ * estimator -- one lane per aircraft, fp64.  K [FD_NLQK][n] as fdyn_lqr_design writes it, F [FD_NKF][n] as fdyn_kf_design writes
+ * it; feedback = FD_LQG_*; zre, zim [n_omega], 1 <= n_omega <= 256 (else FDYN_ERR_BAD_SIZE), shared by all lanes: the points
+ * z = exp(j omega dt) of the unit circle, cos and sin taken by the caller (the kernel sees neither dt nor omega, and uses only
+ * + - * / and sqrt).  Per block (Phi, Gamma, L of F; Kb = the block's 2 x 4 rows of K) and grid point:
+ *   G = (z I - Phi)^-1 Gamma;  L_i = Kb G under measurement or truth feedback;  under estimate feedback
+ *   L_i = z Kb (z I - F_c)^-1 L G with F_c = (I - L) (Phi - Gamma Kb), which is fdyn_lqg_step_*'s loop written out
+ *   (xhat_k = (I - L) (Phi xhat_k-1 + Gamma du_k-1) + L y_k, du_k = -K xhat_k), opened at the plant input.
+ *   Each solve is a complex 4 x 4 elimination with partial pivoting, pivot size |re| + |im|, a pivot below 1e-14 max|matrix| =
+ *   singular.  M = I + L_i is 2 x 2: with F = |M|_F^2, D2 = |det M|^2, s_max^2 = (F + sqrt(max(F^2 - 4 D2, 0))) / 2,
+ *   sigma_min(M) = sqrt(D2) / s_max;  1 / sigma_max(T) of T = L_i M^-1 = L_i adj(M) / det M = sqrt(D2) / s_max(L_i adj(M)).
+ * Outputs, block-major [2][n]: alpha_s = min over the grid of sigma_min(I + L_i) and idx_s (int32) the first grid index attaining
+ * it; alpha_t = min of 1 / sigma_max(T) (+inf where L_i = 0) and idx_t; curve [2][n_omega][n] or NULL: sigma_min(I + L_i) at
+ * every point; status [n] int32 (FD_MRG_* bits).  Status 0 is a guarantee: the nominal loop is Schur (a power of its matrix has
+ * |.|_inf < 1), and for every diagonal perturbation of the two control channels with gains in [1 / (1 + a), 1 / (1 - a)] or
+ * phases up to 2 asin(a / 2), a <= alpha_s, I + L_i Delta stays nonsingular at the grid points, so no pole crosses the circle
+ * there (between grid points: DESIGN.md 7h).  A lane with SINGULAR or BAD_INPUT gets NaN in every alpha and curve word and -1
+ * in every index.  Neither synchronises nor allocates.                                                                        */
+int fdyn_loop_margins(const double* K, const double* F, int feedback, const double* zre, const double* zim, int n_omega, int64_t n,
+                      double* alpha_s, int32_t* idx_s, double* alpha_t, int32_t* idx_t, double* curve, int32_t* status, void* stream);
+
+
 /* ---- sensor layer (csrc/sensor_kernels.hip) ---------------------------------------------------------------------------
  * NoisySensorInterface.update (interfaces/sensor.py:199-243) for n aircraft: meas [FD_NMS][n] = the 12 state words +
  * airspeed + altitude with Gaussian noise, body rates additionally offset by the gyro bias; bias [FD_NSB][n]

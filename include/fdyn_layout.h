@@ -287,6 +287,15 @@ enum { FD_KF_NOT_CONVERGED = 1, FD_KF_NO_CERTIFICATE = 2, FD_KF_BAD_INPUT = 4 };
 /* what the LQG loop feeds back: the filter's estimate, the raw measurement, or the true state (= fdyn_lqr_step_*)         */
 enum { FD_LQG_ESTIMATE = 0, FD_LQG_MEASUREMENT = 1, FD_LQG_TRUTH = 2 };
 
+/* ---- loop margins (fdyn_loop_margins, csrc/margin_kernels.hip) -------------------------------------------------------- */
+/* status bits of a margin report; 0 = the disk guarantee holds (include/fdyn.h)
+ *   NOT_STABLE  the nominal closed loop has no certificate: no power M^(2^k), k <= 30, of Phi - Gamma Kb (under estimate
+ *               feedback: nor of (I - L) Phi) has |.|_inf < 1, or a word of it stopped being finite.  alpha is still written
+ *   SINGULAR    a solve met a pivot below 1e-14 max|matrix| or a grid point gave a non-finite value (a pole on the circle):
+ *               every alpha and curve word of the lane is NaN, every index -1
+ *   BAD_INPUT   a word of K or F that is read is not finite: nothing was computed, the outputs as for SINGULAR               */
+enum { FD_MRG_NOT_STABLE = 1, FD_MRG_SINGULAR = 2, FD_MRG_BAD_INPUT = 4 };
+
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
 enum {
