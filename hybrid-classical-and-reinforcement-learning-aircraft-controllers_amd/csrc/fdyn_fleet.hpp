@@ -47,6 +47,44 @@ FD_DEV int lane_type(const uint8_t* __restrict__ type, int64_t i, int n_types)
     return t < n_types ? t : n_types - 1;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// device: store policy
+// ---------------------------------------------------------------------------------------------------------
+// A kernel's output store with its cache policy chosen at compile time.  WT = false is the plain store.  WT = true is a
+// WRITE-THROUGH store (a relaxed agent-scope atomic store: `global_store_* ... sc1`, no fence and no wait added): the bytes
+// leave the XCD's L2 while the kernel still runs instead of sitting there dirty until the launch's closing release writes
+// them back with every SIMD idle.  For output that the launch itself never reads again and whose volume is a sizeable part
+// of L2 (the env step at one wave per SIMD: 17 MB of 32); loads are not touched.
+template <bool WT, typename T>
+FD_DEV void put(T* p, T v)
+{
+    if constexpr (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+// FD_PUT(WT, lvalue, value): `lvalue = value` under the policy WT, for code that is instantiated both ways.  A macro, so that
+// the WT = false branch is the assignment itself: a call evaluates the address before the value, an assignment the value
+// first, and with the operands born in another order the scheduler's ties fall differently -- the plain instantiations
+// would no longer compile to the instructions they had before the policy existed.
+#define FD_PUT(WT, dst, val) do { if constexpr (WT) fdyn::put<true>(&(dst), (val)); else (dst) = (val); } while (0)
+// The 16-byte write-through store (there is no 16-byte atomic store), for a wave that writes one contiguous range: `base` and
+// `bytes` are wave-uniform, `off` is the lane's byte offset inside the range; the buffer descriptor drops a lane at or past
+// `bytes`.  `buffer_store_dwordx4 ... offen sc1`.
+FD_DEV void put16_through(float* base, uint32_t bytes, uint32_t off, const float4& v)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    // the descriptor lives in scalar registers: say that the base is wave-uniform where the compiler cannot see it
+    // (the builtin returns a signed int: each half goes through uint32_t, or a low word with bit 31 set sign-extends into
+    // the high one)
+    const uint64_t b = reinterpret_cast<uint64_t>(base);
+    const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(b))));
+    const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(b >> 32))));
+    base = reinterpret_cast<float*>(uint64_t(lo) | (uint64_t(hi) << 32));
+    bytes = uint32_t(__builtin_amdgcn_readfirstlane(int(bytes)));
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, int(bytes), 0x00020000);
+    const u32x4 w = { __float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w) };
+    __builtin_amdgcn_raw_buffer_store_b128(w, rsrc, int(off), 0, 16 /* sc1 */);
+}
+
 // Glue type of the agents and control laws: the storage type for the fp64 parity variant, the COMPUTE type for the
 // fp32-evaluation variants (their PIDs take fp32 inputs anyway; round 1 ran the glue in fp64 -- ocml sincos / atan2 / fmod
 // several times per control step -- and the glue cost more than the physics: 7.3 us per control step of which 3.1 us were the RK4).

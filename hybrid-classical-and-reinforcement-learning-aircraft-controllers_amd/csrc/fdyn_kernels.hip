@@ -748,6 +748,8 @@ __device__ __forceinline__ void fetch_reset_record(const double* __restrict__ po
 }
 
 // coalesced write-out of a wave's 64 x 18 observation tile through LDS (row stride 19 words: conflict-free)
+// WT: the store policy (put / put16_through, fdyn_fleet.hpp), on both paths
+template <bool WT = false>
 __device__ __forceinline__ void store_obs_tile(float* tile /*[64*19]*/, const float (&o)[FD_OBS_DIM], int lane,
                                                float* __restrict__ obs_out, int64_t wave_first, int64_t n)
 {
@@ -764,10 +766,17 @@ __device__ __forceinline__ void store_obs_tile(float* tile /*[64*19]*/, const fl
         for (int k = 0; k < FD_OBS_DIM / 2; ++k) row[k] = make_float2(o[2 * k], o[2 * k + 1]);
         __builtin_amdgcn_wave_barrier();
         const float4* t4 = reinterpret_cast<const float4*>(tile);
-        float4* d4 = reinterpret_cast<float4*>(dst);
+        if constexpr (WT) {
+            constexpr uint32_t TILE_BYTES = FD_WAVE * FD_OBS_DIM * sizeof(float);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) d4[j * FD_WAVE + lane] = t4[j * FD_WAVE + lane];
-        if (lane < FD_WAVE / 2) d4[4 * FD_WAVE + lane] = t4[4 * FD_WAVE + lane];
+            for (int j = 0; j < 4; ++j) put16_through(dst, TILE_BYTES, uint32_t(j * FD_WAVE + lane) * 16u, t4[j * FD_WAVE + lane]);
+            if (lane < FD_WAVE / 2) put16_through(dst, TILE_BYTES, uint32_t(4 * FD_WAVE + lane) * 16u, t4[4 * FD_WAVE + lane]);
+        } else {
+            float4* d4 = reinterpret_cast<float4*>(dst);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d4[j * FD_WAVE + lane] = t4[j * FD_WAVE + lane];
+            if (lane < FD_WAVE / 2) d4[4 * FD_WAVE + lane] = t4[4 * FD_WAVE + lane];
+        }
         __builtin_amdgcn_wave_barrier();
         return;
     }
@@ -778,7 +787,7 @@ __device__ __forceinline__ void store_obs_tile(float* tile /*[64*19]*/, const fl
     for (int k = 0; k < FD_OBS_DIM; ++k) {
         const int flat = k * FD_WAVE + lane;
         const int row = flat / FD_OBS_DIM, col = flat - row * FD_OBS_DIM;
-        if (row < valid) dst[flat] = tile[row * (FD_OBS_DIM + 1) + col];
+        if (row < valid) FD_PUT(WT, dst[flat], tile[row * (FD_OBS_DIM + 1) + col]);
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -962,6 +971,14 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
                      float* __restrict__ ev_flt, int ev_cap, int64_t n, DRA... dra)
 {
     constexpr bool DR = sizeof...(DRA) != 0;
+    // The image entry points at one wave per SIMD write the state, the fp64 reward, the observation tile, the PID state and
+    // actions_out THROUGH L2 (FD_PUT / put16_through, fdyn_fleet.hpp): 11 of the 17 MB a launch stores, all of it issued in a
+    // wave's last 2 us, otherwise sit dirty in L2 until the launch's closing release writes them back with every SIMD idle.
+    // The env words, the two integer words and the fp32 reward stay plain -- 4-byte write-through stores are the expensive
+    // kind, and with them the step measured no faster (profiles/env_store_policy_measured.md) -- and so do the flags, the
+    // event records and the counters (131 KB in all).  The plain entry points and the register-capped build (whose output
+    // exceeds L2 anyway) keep plain stores and their text.
+    constexpr bool WT = PREP && !OCC2;
     S* dr = nullptr;
     const double* drc = nullptr;
     if constexpr (DR) dr_unpack(dr, drc, dra...);
@@ -1076,8 +1093,8 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
             a_in[0] = float(sf.aileron); a_in[1] = float(sf.elevator); a_in[2] = float(sf.rudder); a_in[3] = float(sf.throttle);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                pid_state[(k * FD_NPS + 0) * n + i] = st[k].integral; pid_state[(k * FD_NPS + 1) * n + i] = st[k].err_prev;
-                pid_state[(k * FD_NPS + 2) * n + i] = st[k].dfilt;
+                FD_PUT(WT, pid_state[(k * FD_NPS + 0) * n + i], st[k].integral); FD_PUT(WT, pid_state[(k * FD_NPS + 1) * n + i], st[k].err_prev);
+                FD_PUT(WT, pid_state[(k * FD_NPS + 2) * n + i], st[k].dfilt);
             }
             if (residual_mode) {                      // float32 arithmetic, as the reference's NumPy float32 arrays
 #pragma clang fp contract(off)
@@ -1092,7 +1109,11 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
                 res_bonus = S(0.05) * (S(1) - S(mag) / S(3));   // small-correction bonus (:153-154); fp32 magnitude only
             }
         }
-        if (actions_out) reinterpret_cast<float4*>(actions_out)[i] = make_float4(a_in[0], a_in[1], a_in[2], a_in[3]);
+        if constexpr (WT) {                                                       // the wave's rows are one contiguous range
+            const int64_t rows = n - lm.wave_first;
+            if (actions_out) put16_through(actions_out + lm.wave_first * FD_ACT_DIM, uint32_t(rows < FD_WAVE ? rows : FD_WAVE) * 16u,
+                                           uint32_t(lane) * 16u, make_float4(a_in[0], a_in[1], a_in[2], a_in[3]));
+        } else if (actions_out) reinterpret_cast<float4*>(actions_out)[i] = make_float4(a_in[0], a_in[1], a_in[2], a_in[3]);
         S a[4];                                                                   // rate_env.py:225
         a[0] = clipv(S(a_in[0]), S(-1), S(1)); a[1] = clipv(S(a_in[1]), S(-1), S(1));
         a[2] = clipv(S(a_in[2]), S(-1), S(1)); a[3] = clipv(S(a_in[3]), S(0), S(1));
@@ -1192,7 +1213,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
         done = term || trunc;
         env_observation<S, A, E>(x, e, airspeed, altitude, o);
         if (reward_f32) reward_f32[i] = float(reward);
-        if (reward_full) reward_full[i] = reward;
+        if (reward_full) FD_PUT(WT, reward_full[i], reward);
         terminated[i] = term ? 1 : 0;
         truncated[i] = trunc ? 1 : 0;
     }
@@ -1248,10 +1269,10 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
             airspeed_altitude<A0>(xa, airspeed, altitude);
             if constexpr (DR) airspeed = air_speed<A0, S>(x, wair);
             env_observation<S, A0, E>(x, e, airspeed, altitude, o);
-            if (pid_mode) for (int k = 0; k < 3 * FD_NPS; ++k) pid_state[k * n + i] = 0.0f;   // pid_agent.reset()
+            if (pid_mode) for (int k = 0; k < 3 * FD_NPS; ++k) FD_PUT(WT, pid_state[k * n + i], 0.0f);   // pid_agent.reset()
         }
 #pragma unroll
-        for (int k = 0; k < FD_NX; ++k) xs[k * n + i] = x[k];
+        for (int k = 0; k < FD_NX; ++k) FD_PUT(WT, xs[k * n + i], x[k]);
         env_store<E>(e, es, n, i, uses_sched);
         eis[FD_EI_STEP * n + i] = step;
         eis[FD_EI_EPISODE * n + i] = episode;
@@ -1275,7 +1296,7 @@ rate_env_step_kernel(S* __restrict__ xs, typename EnvOf<S, T>::type* __restrict_
         }
     }
     FD_STAMP(4)
-    store_obs_tile(s_tile[wave], o, lane, obs_out, lm.wave_first, n);
+    store_obs_tile<WT>(s_tile[wave], o, lane, obs_out, lm.wave_first, n);
     FD_STAMP(5)
 #ifdef FD_PHASE_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
