@@ -4,95 +4,46 @@ There is NO CPU fallback: if the HIP library is missing or a GPU is not present,
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FDYN_LIB", os.path.join(_HERE, "csrc", "libfdyn_hip.so"))   # FDYN_LIB: A/B experiment builds
 
-FDYN_OK, FDYN_ERR_BAD_DT, FDYN_ERR_BAD_TYPES, FDYN_ERR_BAD_SIZE, FDYN_ERR_NULL = 0, -1, -2, -3, -4
+_SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "float": C.c_float}
 
-_p = C.c_void_p
-_i, _i64, _u64, _d, _f = C.c_int, C.c_int64, C.c_uint64, C.c_double, C.c_float
 
-_SIXDOF = [_p, _p, _p, _p, _i, _i64, _d, _i, _p, _p]
-_CASCADE = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
-_AGENT = [_i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i64, _d, _i, _p, _p]
-_HYBRID = [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i64, _d, _p]
-_LQR_STEP = [_p, _p, _p, _p, _p, _p, _i, _i64, _d, _i, _p, _p, _p]
-# + F, sigma, xhat, du_prev, seed, step, z, feedback, err_est, err_meas, chatter, meas_out before the stream
-_LQG_STEP = _LQR_STEP[:-1] + [_p, _p, _p, _p, _u64, _p, _p, _i, _p, _p, _p, _p, _p]
-_ENV_RESET = [_p, _p, _p, _p, _p, _p, _p, _i, _u64, _p, _i64, _p]
-_ENV_STEP = [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _u64, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-             _i, _i64, _p]
-_ENV_RESET_DR = _ENV_RESET[:-1] + [_p, _p, _p]               # + dr, dr_consts before the stream
-_ENV_STEP_DR = _ENV_STEP[:-1] + [_p, _p, _p]
-_ENV_STEP_IMG = _ENV_STEP[:-1] + [_p, _p]                   # + the prepared launch image before the stream
-_ENV_STEP_DR_IMG = _ENV_STEP_DR[:-1] + [_p, _p]
+def _parse_header(src):
+    """The text of include/fdyn.h -> ({name: (restype, [argtypes])} of every fdyn_* prototype, {name: value} of every integer
+    `#define FDYN_*`).  Strict: a parameter or a declaration it cannot type is a ValueError, never a guess."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
+    consts = {name: int(val) for name, val in re.findall(r"^[ \t]*#define[ \t]+(FDYN_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", src, flags=re.M)}
+    src = re.sub(r"^[ \t]*#define(?:.*\\\n)*.*$", "", src, flags=re.M)          # a macro body declares nothing
+    table = {}
+    for res, name, params in re.findall(r"\b(int|int64_t)\s+(fdyn_\w+)\s*\(([^()]*)\)\s*;", src):
+        args = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            words = param.replace("*", " * ").split()
+            scalar = [w for w in words[:-1] if w != "const"]                  # the last word is the parameter's name
+            if "*" in words:
+                args.append(C.c_void_p)
+            elif len(scalar) == 1 and scalar[0] in _SCALARS:
+                args.append(_SCALARS[scalar[0]])
+            else:
+                raise ValueError(f"include/fdyn.h: {name}: no ctypes type for the parameter '{param.strip()}'")
+        table[name] = (_SCALARS[res], args)
+    heads = re.findall(r"\b(fdyn_\w+)\s*\(", src)
+    if len(heads) != len(table):                 # another return type, a function pointer, a name declared twice
+        raise ValueError(f"include/fdyn.h: {len(heads)} fdyn_* prototype heads, {len(table)} parsed; look at "
+                         f"{sorted(set(heads) - set(table)) or sorted(h for h in set(heads) if heads.count(h) > 1)}")
+    return table, consts
 
-SIGNATURES = {
-    "fdyn_abi_version": (_i, []),
-    "fdyn_num_substeps": (_i, [_d, _d]),
-    "fdyn_device_info": (_i, [C.POINTER(_i), C.POINTER(_i), C.c_char_p, _i]),
-    "fdyn_event_capacity": (_i64, [_i64]),
-    "fdyn_sixdof_step_f64": (_i, _SIXDOF), "fdyn_sixdof_step_mixed": (_i, _SIXDOF), "fdyn_sixdof_step_f32": (_i, _SIXDOF),
-    "fdyn_derived_f64": (_i, [_p, _i64, _p, _p]), "fdyn_derived_f32": (_i, [_p, _i64, _p, _p]),
-    "fdyn_pid_compute_batch": (_i, [_p, _i, _p, _p, _p, _f, _p, _i64, _p]),
-    "fdyn_cascade_step_f64": (_i, _CASCADE), "fdyn_cascade_step_mixed": (_i, _CASCADE), "fdyn_cascade_step_f32": (_i, _CASCADE),
-    "fdyn_rate_env_reset_f64": (_i, _ENV_RESET), "fdyn_rate_env_reset_mixed": (_i, _ENV_RESET),
-    "fdyn_rate_env_reset_f32": (_i, _ENV_RESET),
-    "fdyn_rate_env_step_f64": (_i, _ENV_STEP), "fdyn_rate_env_step_mixed": (_i, _ENV_STEP),
-    "fdyn_rate_env_step_f32": (_i, _ENV_STEP),
-    "fdyn_rate_env_reset_dr_f64": (_i, _ENV_RESET_DR), "fdyn_rate_env_reset_dr_mixed": (_i, _ENV_RESET_DR),
-    "fdyn_rate_env_reset_dr_f32": (_i, _ENV_RESET_DR),
-    "fdyn_rate_env_step_dr_f64": (_i, _ENV_STEP_DR), "fdyn_rate_env_step_dr_mixed": (_i, _ENV_STEP_DR),
-    "fdyn_rate_env_step_dr_f32": (_i, _ENV_STEP_DR),
-    "fdyn_rate_env_image": (_i, [_p, _i, _p, _i, _p, _p]),
-    "fdyn_rate_env_step_img_f64": (_i, _ENV_STEP_IMG), "fdyn_rate_env_step_img_mixed": (_i, _ENV_STEP_IMG),
-    "fdyn_rate_env_step_img_f32": (_i, _ENV_STEP_IMG),
-    "fdyn_rate_env_step_dr_img_f64": (_i, _ENV_STEP_DR_IMG), "fdyn_rate_env_step_dr_img_mixed": (_i, _ENV_STEP_DR_IMG),
-    "fdyn_rate_env_step_dr_img_f32": (_i, _ENV_STEP_DR_IMG),
-    "fdyn_lstm_cell_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
-    "fdyn_lstm_cell_bwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
-    "fdyn_lstm_seq_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i, _p]),
-    "fdyn_lstm_seq_bwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i, _p]),
-    "fdyn_lstm_seq_bwd_bsum": (_i, [_p, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i, _p]),
-    "fdyn_lstm_seq_bwd_pre": (_i, [_p, _i, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i, _p]),
-    "fdyn_lstm_cell0_fwd": (_i, [_p, _i, _p, _p, _i64, _i, _p]),
-    "fdyn_lstm_cell0_bwd": (_i, [_p, _i, _p, _p, _p, _i64, _i64, _i, _p]),
-    "fdyn_colsum_partials": (_i, [_p, _i64, _i, _p, _p, _p]),
-    "fdyn_episode_flags": (_i, [_p, _p, _p, _p, _p, _i64, _p]),
-    "fdyn_policy_trunks": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
-    "fdyn_policy_trunks_heads": (_i, [_p] * 11 + [_u64, _p, _i, _p, _p, _p, _i64, _p]),
-    "fdyn_agent_step_f64": (_i, _AGENT), "fdyn_agent_step_mixed": (_i, _AGENT), "fdyn_agent_step_f32": (_i, _AGENT),
-    "fdyn_hybrid_step_f64": (_i, _HYBRID), "fdyn_hybrid_step_mixed": (_i, _HYBRID), "fdyn_hybrid_step_f32": (_i, _HYBRID),
-    "fdyn_colsum_ws_floats": (_i64, [_i64, _i, _i64, _i]),
-    "fdyn_colsum": (_i, [_p, _i, _i64, _i, _i64, _i, _p, _p, _p]),
-    "fdyn_ppo_loss": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _f, _i64, _p, _p, _p, _p, _p]),
-    "fdyn_lstm_cell_mfma": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
-    "fdyn_lstm_cell_mfma_inplace_ok": (_i, [_i, _i, _i, _i64]),
-    "fdyn_lstm_cell_mfma_pair": (_i, [_p, _i, _p, _i, _i64, _i] + [_p] * 13),
-    "fdyn_lstm_cell_mfma_train": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i, _p]),
-    "fdyn_policy_features_image_bytes": (_i, []),
-    "fdyn_policy_features": (_i, [_p, _p, _p, _p, _i64, _p]),
-    "fdyn_policy_features_flags": (_i, [_p] * 9 + [_i64, _p]),
-    "fdyn_gaussian_head": (_i, [_p, _i, _p, _u64, _p, _i, _p, _p, _i64, _p]),
-    "fdyn_policy_heads": (_i, [_p, _p, _p, _p, _p, _p, _p, _u64, _p, _i, _p, _p, _p, _i64, _p]),
-    "fdyn_gae": (_i, [_p, _p, _p, _p, _p, _f, _f, _i, _i64, _p, _p, _p]),
-    "fdyn_rate_metrics_f64": (_i, [_p, _p, _p, _p, _p, _p, _d, _i, _i, _i64, _p, _p]),
-    "fdyn_rate_reward_seq_f64": (_i, [_p, _p, _p, _p, _p, _p, _p, _d, _i, _i64, _p, _p, _p, _p, _p]),
-    "fdyn_rate_reward_seq_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _f, _i, _i64, _p, _p, _p, _p, _p]),
-    "fdyn_sensor_update_f64": (_i, [_p, _p, _p, _p, _p, _u64, _p, _p, _i64, _p]),
-    "fdyn_sensor_update_f32": (_i, [_p, _p, _p, _p, _p, _u64, _p, _p, _i64, _p]),
-    "fdyn_sensor_observe": (_i, [_p, _p, _p, _p, _p, _u64, _p, _i64, _p]),
-    "fdyn_rate_metrics_f32": (_i, [_p, _p, _p, _p, _p, _p, _d, _i, _i, _i64, _p, _p]),
-    "fdyn_traj_compare": (_i, [_p, _i, _p, _p, _i, _p, _i, _i64, _p, _p, _p]),
-    "fdyn_trim": (_i, [_p, _p, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p]),
-    "fdyn_linearize": (_i, [_p, _p, _i, _p, _p, _p, _i, _i64, _p, _p, _p]),
-    "fdyn_lqr_design": (_i, [_p, _p, _p, _i, _i64, _p, _p, _p, _p, _p]),
-    "fdyn_lqr_step_f64": (_i, _LQR_STEP), "fdyn_lqr_step_mixed": (_i, _LQR_STEP), "fdyn_lqr_step_f32": (_i, _LQR_STEP),
-    "fdyn_kf_design": (_i, [_p, _p, _d, _p, _i, _i64, _p, _p, _p, _p, _p]),
-    "fdyn_lqg_step_f64": (_i, _LQG_STEP), "fdyn_lqg_step_mixed": (_i, _LQG_STEP), "fdyn_lqg_step_f32": (_i, _LQG_STEP),
-    "fdyn_loop_margins": (_i, [_p, _p, _i, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p, _p]),
-}
+
+# name -> (restype, [argtypes]), and FDYN_OK, FDYN_ERR_*, FDYN_ABI_VERSION: read from the header the library is compiled against,
+# as layout.py reads fdyn_layout.h.  Every pointer is c_void_p, the three host pointers of fdyn_device_info included: nothing in the
+# repository calls it from Python.
+with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn.h")) as _f:
+    SIGNATURES, _CONSTS = _parse_header(_f.read())
+globals().update(_CONSTS)
 
 _lib = None
 
@@ -112,7 +63,7 @@ def load():
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
-        if lib.fdyn_abi_version() != 3:
+        if lib.fdyn_abi_version() != FDYN_ABI_VERSION:
             raise FdynError("libfdyn_hip.so ABI version mismatch")
         _lib = lib
     return _lib

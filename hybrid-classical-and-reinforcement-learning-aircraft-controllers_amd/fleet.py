@@ -19,6 +19,7 @@ from .params import AircraftParams, param_table
 
 class BatchedSixDOF:
     _trim = None                 # (TrimResult, scales) of the last .trim(): the point design_lqr designs at
+    _lqr = _kalman = lqr_saturated_steps = None     # the last design_lqr() / design_kalman(); [N] int32 once an LQR / LQG step ran
 
     def __init__(self, n: int, precision: str = "f64", types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, device=None):
@@ -107,9 +108,7 @@ class BatchedSixDOF:
         LqrWeights, or penalties [12] / [12][N]; scales: None = the multipliers the trim was solved with.  strict: raise
         ValueError when an aircraft has no certified gain.  The fleet's state is not touched."""
         from . import lqr as Q
-        if self._trim is None:
-            raise ValueError(f"{type(self).__name__}.design_lqr: the fleet has no trim; call .trim(...) first")
-        res, trim_scales = self._trim
+        res, trim_scales = self._need_trim("design_lqr")
         out = Q.design_lqr(res, self.params, self.type_index, trim_scales if scales is None else scales, weights)
         if strict:
             Q.require_ok(out, f"{type(self).__name__}.design_lqr")
@@ -124,9 +123,7 @@ class BatchedSixDOF:
         from . import lqr as Q
         if dt is None:
             dt = getattr(self, "dt", 0.01)
-        if getattr(self, "lqr_saturated_steps", None) is None:
-            self.lqr_saturated_steps = torch.zeros(self.n, dtype=torch.int32, device=self.device)
-        Q.step_into(self.precision, self.x, design, self.params, self.type_index, dt, n_steps, self.u, self.lqr_saturated_steps)
+        Q.step_into(self.precision, self.x, design, self.params, self.type_index, dt, n_steps, self.u, self._saturated_steps())
         self.time += dt * n_steps
 
     # LQG (hcrl_amd.lqg): the estimator beside the LQR, and the output-feedback loop on noisy measurements
@@ -136,9 +133,7 @@ class BatchedSixDOF:
         process-noise rates), a KalmanNoise, or [16] / [16][N]; scales as design_lqr.  strict: raise ValueError when an aircraft
         has no certified filter.  Also starts the loop's state (`lqg`: estimate at the trim, step word 0)."""
         from . import lqg as G
-        if self._trim is None:
-            raise ValueError(f"{type(self).__name__}.design_kalman: the fleet has no trim; call .trim(...) first")
-        res, trim_scales = self._trim
+        res, trim_scales = self._need_trim("design_kalman")
         out = G.design_kalman(res, self.params, self.type_index, trim_scales if scales is None else scales, dt, noise)
         if strict:
             G.require_ok(out, f"{type(self).__name__}.design_kalman")
@@ -153,15 +148,9 @@ class BatchedSixDOF:
         float64 standard normals.  `u` receives the last applied controls, `lqr_saturated_steps` counts clipped steps, `lqg`
         carries the estimate and the accumulators (err_est, err_meas, chatter)."""
         from . import lqg as G
-        lqr_design, kalman = getattr(self, "_lqr", None), getattr(self, "_kalman", None)
-        if lqr_design is None or kalman is None:
-            missing = "design_lqr()" if lqr_design is None else "design_kalman(dt)"
-            raise ValueError(f"{type(self).__name__}.step_lqg: {self.n} of {self.n} aircraft have no certified "
-                             f"{'stabilising gain' if lqr_design is None else 'stable filter'} (call .{missing} first)")
-        if getattr(self, "lqr_saturated_steps", None) is None:
-            self.lqr_saturated_steps = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        lqr_design, kalman = self._need_designs("step_lqg")
         G.step_into(self.precision, self.x, lqr_design, kalman, self.lqg, self.params, self.type_index, kalman.dt, n_steps, feedback, z,
-                    self.u, self.lqr_saturated_steps)
+                    self.u, self._saturated_steps())
         self.time += kalman.dt * n_steps
 
     # Loop margins (hcrl_amd.margins): how robust the loop step_lqr / step_lqg fly is, sampled at dt and through the estimator
@@ -171,12 +160,23 @@ class BatchedSixDOF:
         phase disk it stands for is guaranteed.  Needs design_lqr() and design_kalman() first.  omega: None = 64 points,
         logarithmic from 0.01 rad/s to the Nyquist rate.  The fleet's state is not touched."""
         from . import margins as M
-        lqr_design, kalman = getattr(self, "_lqr", None), getattr(self, "_kalman", None)
-        if lqr_design is None or kalman is None:
-            missing = "design_lqr()" if lqr_design is None else "design_kalman(dt)"
-            raise ValueError(f"{type(self).__name__}.loop_margins: {self.n} of {self.n} aircraft have no certified "
-                             f"{'stabilising gain' if lqr_design is None else 'stable filter'} (call .{missing} first)")
-        return M.loop_margins(lqr_design, kalman, feedback, omega, curve)
+        return M.loop_margins(*self._need_designs("loop_margins"), feedback, omega, curve)
+
+    def _need_trim(self, what: str):
+        if self._trim is None:
+            raise ValueError(f"{type(self).__name__}.{what}: the fleet has no trim; call .trim(...) first")
+        return self._trim
+
+    def _need_designs(self, what: str):
+        for design, lacks, call in ((self._lqr, "stabilising gain", "design_lqr()"), (self._kalman, "stable filter", "design_kalman(dt)")):
+            if design is None:
+                raise ValueError(f"{type(self).__name__}.{what}: {self.n} of {self.n} aircraft have no certified {lacks} (call .{call} first)")
+        return self._lqr, self._kalman
+
+    def _saturated_steps(self) -> torch.Tensor:
+        if self.lqr_saturated_steps is None:
+            self.lqr_saturated_steps = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        return self.lqr_saturated_steps
 
 
 class BatchedCascade(BatchedSixDOF):

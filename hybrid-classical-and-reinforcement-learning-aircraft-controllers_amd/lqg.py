@@ -31,12 +31,6 @@ FEEDBACK = {"estimate": L.FD_LQG_ESTIMATE, "measurement": L.FD_LQG_MEASUREMENT, 
 DEFAULT_RATES = (0.1, 0.1, 0.05, 0.005, 0.1, 0.05, 0.05, 0.005)     # s of (u, w, q, theta | v, p, r, phi), state units per sqrt(s)
 
 
-def describe_status(status: int) -> str:
-    """'ok' or the names of the FD_KF_* bits set in one status word."""
-    names = [name for bit, name in STATUS_BITS if int(status) & bit]
-    return ", ".join(names) if names else "ok"
-
-
 def sensor_sigma(noise_config: Optional[dict] = None) -> np.ndarray:
     """[8] float64: the sensor layer's standard deviations on (u, w, q, theta | v, p, r, phi) -- GPS velocity on the body
     velocities, gyro on the rates, attitude on the two angles -- from a `NoisySensorInterface` noise_config (None: its defaults)."""
@@ -46,32 +40,22 @@ def sensor_sigma(noise_config: Optional[dict] = None) -> np.ndarray:
 
 
 @dataclass
-class KalmanNoise:
+class KalmanNoise(T.LaneTable):
     """What the filter is designed for: the measurement standard deviations (from a sensor noise_config, or given) and the
     process-noise rates s in state units per sqrt(s).  Every entry of `sigma` and `rates` a scalar, or a length-n array for a
     sweep in one launch (`rows`)."""
     noise_config: Optional[dict] = None
     sigma: Optional[tuple] = None              # 8 entries; None: sensor_sigma(noise_config)
     rates: tuple = DEFAULT_RATES
+    ENTRY = "Kalman noise entry"
 
     def _entries(self):
+        """sigma then rates, [FD_NKFN] in FD_KFN_* order: what `vector` and `rows` return as given."""
         sigma = tuple(sensor_sigma(self.noise_config)) if self.sigma is None else tuple(self.sigma)
         rates = tuple(self.rates)
         if len(sigma) != 8 or len(rates) != 8:
             raise ValueError("KalmanNoise: sigma and rates have 8 entries each (u, w, q, theta | v, p, r, phi)")
         return sigma + rates
-
-    @property
-    def per_lane(self) -> bool:
-        return any(np.ndim(v.detach().cpu() if isinstance(v, torch.Tensor) else v) > 0 for v in self._entries())
-
-    def vector(self) -> np.ndarray:
-        """[FD_NKFN] float64 (every entry a scalar)."""
-        return np.array([float(np.asarray(v).reshape(())) for v in self._entries()], dtype=np.float64)
-
-    def rows(self, n: int) -> np.ndarray:
-        """[FD_NKFN][n] float64: scalars broadcast, length-n arrays taken per aircraft."""
-        return T.broadcast_rows(n, self._entries(), "Kalman noise entry")
 
 
 def noise_tensor(noise, n: int, device) -> torch.Tensor:
@@ -80,31 +64,20 @@ def noise_tensor(noise, n: int, device) -> torch.Tensor:
         noise = KalmanNoise()
     if isinstance(noise, KalmanNoise):
         return torch.as_tensor(noise.rows(n) if noise.per_lane else noise.vector(), device=device)
-    w = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(np.asarray(noise, np.float64))
-    if tuple(w.shape) not in ((L.FD_NKFN,), (L.FD_NKFN, n)):
-        raise ValueError(f"noise: expected [{L.FD_NKFN}] or [{L.FD_NKFN}][{n}], got {tuple(w.shape)}")
-    return w.to(device=device, dtype=torch.float64).contiguous()
+    return T.table_tensor(noise, n, device, "noise", L.FD_NKFN)
 
 
 @dataclass
-class KalmanDesign:
+class KalmanDesign(T.StatusResult):
+    STATUS_BITS = STATUS_BITS
+    FAILURE = "have no certified stable filter"
+
     F: torch.Tensor                         # [80][n] float64: Phi_lon, Phi_lat, Gamma_lon, Gamma_lat, L_lon, L_lat (FD_KF_*)
     residual: torch.Tensor                  # [n] float64: relative residual of the filter equation, worse block (NaN: invalid input)
     iters: torch.Tensor                     # [n] int32: doubling steps of the slower block
     status: torch.Tensor                    # [n] int32: FD_KF_* bits, 0 = a certified stable filter
     dt: float = 0.0                         # the step the model was discretised at
     sigma: Optional[torch.Tensor] = None    # [8] float64: the measurement noise the loop applies (shared noise only)
-
-    @property
-    def n(self) -> int:
-        return int(self.status.shape[0])
-
-    @property
-    def ok(self) -> torch.Tensor:
-        return self.status == 0
-
-    def count_not_ok(self) -> int:
-        return int((self.status != 0).sum())
 
     def _matrix(self, lon: int, lat: int, cols: int) -> torch.Tensor:
         return torch.stack([self.F[base:base + 4 * cols].reshape(4, cols, self.n) for base in (lon, lat)])
@@ -127,16 +100,13 @@ class KalmanDesign:
         return torch.einsum("bikn,bkjn->bijn", self.phi(), eye - self.gain())
 
 
+describe_status = KalmanDesign.describe_status               # 'ok' or the names of the FD_KF_* bits set in one status word
+
+
 def kalman_into(A: torch.Tensor, B: torch.Tensor, dt: float, noise: torch.Tensor, out: Optional[KalmanDesign] = None) -> KalmanDesign:
     """One launch of fdyn_kf_design on device tensors: A [12][12][n], B [12][4][n], noise [16] or [16][n], all float64; with
     `out` given nothing is allocated (the form to capture in a graph)."""
-    n, dev = int(A.shape[-1]), A.device
-    if tuple(A.shape) != (L.FD_NX, L.FD_NX, n) or tuple(B.shape) != (L.FD_NX, L.FD_NU, n):
-        raise ValueError(f"expected A [12][12][n] and B [12][4][n], got {tuple(A.shape)} and {tuple(B.shape)}")
-    if tuple(noise.shape) not in ((L.FD_NKFN,), (L.FD_NKFN, n)):
-        raise ValueError(f"noise: expected [{L.FD_NKFN}] or [{L.FD_NKFN}][{n}], got {tuple(noise.shape)}")
-    if A.dtype != torch.float64 or B.dtype != torch.float64 or noise.dtype != torch.float64:
-        raise ValueError("A, B and noise must be float64")
+    n, dev = T.check_model(A, B, noise, "noise", L.FD_NKFN), A.device
     if out is None:
         out = KalmanDesign(torch.empty((L.FD_NKF, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
                            torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
@@ -151,21 +121,16 @@ def design_kalman(trim_result, params: torch.Tensor, type_index=None, scales=Non
     """Linearise every aircraft at its trim (fdyn_linearize at x0, u0), then design its filter at step dt.  params, type_index,
     scales as `lqr.design_lqr` takes them; noise as `noise_tensor` takes it.  The loop's own measurement noise (`sigma`) is the
     design's when the noise is shared, else the sensor defaults: set `.sigma` to fly another."""
-    n, dev = trim_result.n, trim_result.x0.device
-    A, B = T.linearize_into(trim_result.x0, trim_result.u0, params, T._type_tensor(n, type_index, dev), T.scale_rows(n, scales, dev))
-    nz = noise_tensor(noise, n, dev)
+    A, B = T.linearize_at_trim(trim_result, params, type_index, scales)
+    nz = noise_tensor(noise, trim_result.n, A.device)
     out = kalman_into(A, B, dt, nz)
-    out.sigma = nz[:8].clone() if nz.dim() == 1 else torch.as_tensor(sensor_sigma(), device=dev)
+    out.sigma = nz[:8].clone() if nz.dim() == 1 else torch.as_tensor(sensor_sigma(), device=A.device)
     return out
 
 
 def require_ok(design: KalmanDesign, what: str = "design_kalman"):
     """ValueError naming how many lanes have no certified filter, and why for the first of them."""
-    bad = design.count_not_ok()
-    if bad:
-        first = int(torch.nonzero(design.status != 0)[0])
-        raise ValueError(f"{what}: {bad} of {design.n} aircraft have no certified stable filter "
-                         f"(first: aircraft {first}: {describe_status(int(design.status[first]))})")
+    design.require_ok(what)
 
 
 @dataclass

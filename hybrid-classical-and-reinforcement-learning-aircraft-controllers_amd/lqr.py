@@ -26,14 +26,8 @@ STATUS_BITS = ((L.FD_LQR_NOT_CONVERGED, "not converged"), (L.FD_LQR_NO_CERTIFICA
                (L.FD_LQR_BAD_INPUT, "invalid model or weights"))
 
 
-def describe_status(status: int) -> str:
-    """'ok' or the names of the FD_LQR_* bits set in one status word."""
-    names = [name for bit, name in STATUS_BITS if int(status) & bit]
-    return ", ".join(names) if names else "ok"
-
-
 @dataclass
-class LqrWeights:
+class LqrWeights(T.LaneTable):
     """Bryson's rule: the largest acceptable excursion of each regulated word and of each control; the penalty is 1 / max^2.
     Scalars, or length-n arrays for a sweep of weight sets in one launch (`rows`)."""
     u: object = 2.0            # m/s
@@ -49,25 +43,19 @@ class LqrWeights:
     aileron: object = 0.3
     rudder: object = 0.3
 
+    ENTRY = "LQR maximum"
+
     def maxima(self):
         """The twelve maxima in FD_LQW_* order."""
         return tuple(getattr(self, f.name) for f in fields(self))
 
-    def vector(self) -> np.ndarray:
-        """[FD_NLQW] float64 penalties (every maximum a scalar)."""
-        m = np.array([float(np.asarray(v).reshape(())) for v in self.maxima()], dtype=np.float64)
+    _entries = maxima
+
+    @staticmethod
+    def _values(m: np.ndarray) -> np.ndarray:
+        """The penalties `vector` [FD_NLQW] and `rows` [FD_NLQW][n] return: 1 / max^2."""
         with np.errstate(all="ignore"):
             return 1.0 / (m * m)
-
-    def rows(self, n: int) -> np.ndarray:
-        """[FD_NLQW][n] float64 penalties: scalars broadcast, length-n arrays taken per aircraft."""
-        m = T.broadcast_rows(n, self.maxima(), "LQR maximum")
-        with np.errstate(all="ignore"):
-            return 1.0 / (m * m)
-
-    @property
-    def per_lane(self) -> bool:
-        return any(np.ndim(v.detach().cpu() if isinstance(v, torch.Tensor) else v) > 0 for v in self.maxima())
 
 
 assert len(fields(LqrWeights)) == L.FD_NLQW
@@ -78,33 +66,21 @@ def weights_tensor(weights, n: int, device) -> torch.Tensor:
     if weights is None:
         weights = LqrWeights()
     if isinstance(weights, LqrWeights):
-        host = weights.rows(n) if weights.per_lane else weights.vector()
-        return torch.as_tensor(host, device=device)
-    w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights, np.float64))
-    if tuple(w.shape) not in ((L.FD_NLQW,), (L.FD_NLQW, n)):
-        raise ValueError(f"weights: expected [{L.FD_NLQW}] or [{L.FD_NLQW}][{n}], got {tuple(w.shape)}")
-    return w.to(device=device, dtype=torch.float64).contiguous()
+        return torch.as_tensor(weights.rows(n) if weights.per_lane else weights.vector(), device=device)
+    return T.table_tensor(weights, n, device, "weights", L.FD_NLQW)
 
 
 @dataclass
-class LqrDesign:
+class LqrDesign(T.StatusResult):
+    STATUS_BITS = STATUS_BITS
+    FAILURE = "have no certified stabilising gain"
+
     K: torch.Tensor                         # [16][n] float64: K_lon 2 x 4 row-major, then K_lat 2 x 4 (FD_LQK_*)
     residual: torch.Tensor                  # [n] float64: relative Riccati residual of the worse block (NaN: invalid input)
     iterations: torch.Tensor                # [n] int32: doubling steps of the slower block
     status: torch.Tensor                    # [n] int32: FD_LQR_* bits, 0 = a certified stabilising gain
     x0: Optional[torch.Tensor] = None       # [12][n] float64: the point the gains regulate to
     u0: Optional[torch.Tensor] = None       # [4][n]  float64
-
-    @property
-    def n(self) -> int:
-        return int(self.status.shape[0])
-
-    @property
-    def ok(self) -> torch.Tensor:
-        return self.status == 0
-
-    def count_not_ok(self) -> int:
-        return int((self.status != 0).sum())
 
     def gain_matrix(self) -> torch.Tensor:
         """[4][12][n]: the feedback matrix on the full state (u = u0 - K (x - x0)), zeros outside the two blocks."""
@@ -121,16 +97,13 @@ class LqrDesign:
         return A - torch.einsum("ikn,kjn->ijn", B, self.gain_matrix())
 
 
+describe_status = LqrDesign.describe_status                  # 'ok' or the names of the FD_LQR_* bits set in one status word
+
+
 def lqr_into(A: torch.Tensor, B: torch.Tensor, weights: torch.Tensor, out: Optional[LqrDesign] = None) -> LqrDesign:
     """One launch of fdyn_lqr_design on device tensors: A [12][12][n], B [12][4][n], weights [12] or [12][n], all float64; with
     `out` given nothing is allocated (the form to capture in a graph)."""
-    n, dev = int(A.shape[-1]), A.device
-    if tuple(A.shape) != (L.FD_NX, L.FD_NX, n) or tuple(B.shape) != (L.FD_NX, L.FD_NU, n):
-        raise ValueError(f"expected A [12][12][n] and B [12][4][n], got {tuple(A.shape)} and {tuple(B.shape)}")
-    if tuple(weights.shape) not in ((L.FD_NLQW,), (L.FD_NLQW, n)):
-        raise ValueError(f"weights: expected [{L.FD_NLQW}] or [{L.FD_NLQW}][{n}], got {tuple(weights.shape)}")
-    if A.dtype != torch.float64 or B.dtype != torch.float64 or weights.dtype != torch.float64:
-        raise ValueError("A, B and weights must be float64")
+    n, dev = T.check_model(A, B, weights, "weights", L.FD_NLQW), A.device
     if out is None:
         out = LqrDesign(torch.empty((L.FD_NLQK, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
                         torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
@@ -143,20 +116,15 @@ def lqr_into(A: torch.Tensor, B: torch.Tensor, weights: torch.Tensor, out: Optio
 def design_lqr(trim_result, params: torch.Tensor, type_index=None, scales=None, weights=None) -> LqrDesign:
     """Linearise every aircraft at its trim (fdyn_linearize at x0, u0), then design.  params [n_types][FD_NP] on the device;
     type_index [n] or None; scales as `trim.scale_rows` takes them; weights as `weights_tensor` takes them."""
-    n, dev = trim_result.n, trim_result.x0.device
-    A, B = T.linearize_into(trim_result.x0, trim_result.u0, params, T._type_tensor(n, type_index, dev), T.scale_rows(n, scales, dev))
-    out = lqr_into(A, B, weights_tensor(weights, n, dev))
+    A, B = T.linearize_at_trim(trim_result, params, type_index, scales)
+    out = lqr_into(A, B, weights_tensor(weights, trim_result.n, A.device))
     out.x0, out.u0 = trim_result.x0, trim_result.u0
     return out
 
 
 def require_ok(design: LqrDesign, what: str = "design_lqr"):
     """ValueError naming how many lanes have no certified gain, and why for the first of them."""
-    bad = design.count_not_ok()
-    if bad:
-        first = int(torch.nonzero(design.status != 0)[0])
-        raise ValueError(f"{what}: {bad} of {design.n} aircraft have no certified stabilising gain "
-                         f"(first: aircraft {first}: {describe_status(int(design.status[first]))})")
+    design.require_ok(what)
 
 
 def step_into(precision: str, x: torch.Tensor, design: LqrDesign, params: torch.Tensor, type_index: Optional[torch.Tensor],

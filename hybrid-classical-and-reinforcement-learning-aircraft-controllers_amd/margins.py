@@ -22,17 +22,12 @@ import torch
 
 from . import _lib, layout as L
 from .lqg import FEEDBACK
+from .trim import StatusResult
 
 STATUS_BITS = ((L.FD_MRG_NOT_STABLE, "nominal loop not certified stable"), (L.FD_MRG_SINGULAR, "a pole on a grid point"),
                (L.FD_MRG_BAD_INPUT, "invalid gain or filter"))
 MAX_OMEGA = 256
 OMEGA_LOW = 1e-2                                                 # rad/s: where the default grid starts
-
-
-def describe_status(status: int) -> str:
-    """'ok' or the names of the FD_MRG_* bits set in one status word."""
-    names = [name for bit, name in STATUS_BITS if int(status) & bit]
-    return ", ".join(names) if names else "ok"
 
 
 def default_grid(dt: float, n: int = 64) -> np.ndarray:
@@ -59,7 +54,9 @@ def unit_circle(omega, dt: float):
 
 
 @dataclass
-class LoopMargins:
+class LoopMargins(StatusResult):
+    STATUS_BITS = STATUS_BITS
+
     alpha_s: torch.Tensor                   # [2][n] float64: min over the grid of sigma_min(I + L_i), longitudinal | lateral
     idx_s: torch.Tensor                     # [2][n] int32: the first grid index attaining it (-1: no margin to report)
     alpha_t: torch.Tensor                   # [2][n] float64: min of 1 / sigma_max(T), the complementary-sensitivity disk
@@ -69,19 +66,6 @@ class LoopMargins:
     omega: Optional[torch.Tensor] = None    # [n_omega] float64 on the device (None: the caller gave z only)
     dt: float = 0.0
     feedback: int = L.FD_LQG_ESTIMATE
-
-    @property
-    def n(self) -> int:
-        return int(self.status.shape[0])
-
-    @property
-    def ok(self) -> torch.Tensor:
-        return self.status == 0
-
-    def count_not_ok(self) -> int:
-        return int((self.status != 0).sum())
-
-    describe_status = staticmethod(describe_status)
 
     def _omega_at(self, idx: torch.Tensor) -> torch.Tensor:
         if self.omega is None:
@@ -114,6 +98,9 @@ class LoopMargins:
         """[2][n]: independent phase changes of both channels up to 2 asin(alpha_s / 2) keep the loop stable (180 where alpha_s >= 2)."""
         a = self.alpha_s
         return torch.where(a == a, torch.rad2deg(2.0 * torch.asin((0.5 * a).clamp(max=1.0))), a)
+
+
+describe_status = LoopMargins.describe_status                # 'ok' or the names of the FD_MRG_* bits set in one status word
 
 
 def margins_into(K: torch.Tensor, F: torch.Tensor, zre: torch.Tensor, zim: torch.Tensor, feedback="estimate",

@@ -33,10 +33,41 @@ LATERAL_STATES = (L.FD_X_V, L.FD_X_P, L.FD_X_R, L.FD_X_ROLL)
 LATERAL_CONTROLS = (L.FD_U_AILERON, L.FD_U_RUDDER)
 
 
-def describe_status(status: int) -> str:
-    """'ok' or the names of the FD_TRIM_* bits set in one status word."""
-    names = [name for bit, name in STATUS_BITS if int(status) & bit]
+def status_names(bits, status: int) -> str:
+    """'ok' or the comma-joined names of the (bit, name) pairs of `bits` that are set in one status word."""
+    names = [name for bit, name in bits if int(status) & bit]
     return ", ".join(names) if names else "ok"
+
+
+class StatusResult:
+    """What TrimResult, LqrDesign, KalmanDesign and LoopMargins share: the reading of their `status` [n] int32.  A subclass names
+    its module's STATUS_BITS and, where it has a strict check, what its failed lanes lack (FAILURE)."""
+    STATUS_BITS = ()
+    FAILURE = "have a non-zero status"
+
+    @property
+    def n(self) -> int:
+        return int(self.status.shape[0])
+
+    @property
+    def ok(self) -> torch.Tensor:
+        return self.status == 0
+
+    def count_not_ok(self) -> int:
+        return int((self.status != 0).sum())
+
+    @classmethod
+    def describe_status(cls, status: int) -> str:
+        """'ok' or the names of the module's status bits set in one status word."""
+        return status_names(cls.STATUS_BITS, status)
+
+    def require_ok(self, what: str):
+        """ValueError naming how many lanes have a non-zero status, and why for the first of them."""
+        bad = self.count_not_ok()
+        if bad:
+            first = int(torch.nonzero(self.status != 0)[0])
+            raise ValueError(f"{what}: {bad} of {self.n} aircraft {self.FAILURE} "
+                             f"(first: aircraft {first}: {self.describe_status(int(self.status[first]))})")
 
 
 def broadcast_rows(n: int, values: Sequence, what: str = "value") -> np.ndarray:
@@ -69,21 +100,61 @@ def scale_rows(n: int, scales, device) -> Optional[torch.Tensor]:
     return torch.as_tensor(broadcast_rows(n, tuple(scales), "scale row"), device=device)
 
 
+class LaneTable:
+    """What LqrWeights and KalmanNoise share: a design table whose `_entries()` are scalars, or length-n arrays for a sweep of
+    tables in one launch (`rows`); `_values` maps the entries to what the kernel reads."""
+    ENTRY = "entry"                                   # what broadcast_rows calls an offending entry
+
+    @staticmethod
+    def _values(entries: np.ndarray) -> np.ndarray:
+        return entries
+
+    @property
+    def per_lane(self) -> bool:
+        return any(np.ndim(v.detach().cpu() if isinstance(v, torch.Tensor) else v) > 0 for v in self._entries())
+
+    def vector(self) -> np.ndarray:
+        """[len(entries)] float64 (every entry a scalar)."""
+        return self._values(np.array([float(np.asarray(v).reshape(())) for v in self._entries()], dtype=np.float64))
+
+    def rows(self, n: int) -> np.ndarray:
+        """[len(entries)][n] float64: scalars broadcast, length-n arrays taken per aircraft."""
+        return self._values(broadcast_rows(n, self._entries(), self.ENTRY))
+
+
+def check_table(table: torch.Tensor, n: int, name: str, rows: int):
+    if tuple(table.shape) not in ((rows,), (rows, n)):
+        raise ValueError(f"{name}: expected [{rows}] or [{rows}][{n}], got {tuple(table.shape)}")
+
+
+def table_tensor(table, n: int, device, name: str, rows: int) -> torch.Tensor:
+    """An array / tensor [rows] or [rows][n] -> contiguous float64 on the device; `name` is the caller's word for it."""
+    w = table if isinstance(table, torch.Tensor) else torch.as_tensor(np.asarray(table, np.float64))
+    check_table(w, n, name, rows)
+    return w.to(device=device, dtype=torch.float64).contiguous()
+
+
+def check_model(A: torch.Tensor, B: torch.Tensor, table: torch.Tensor, name: str, rows: int) -> int:
+    """n of a linear model A [12][12][n], B [12][4][n] and its design table [rows] or [rows][n], all float64."""
+    n = int(A.shape[-1])
+    if tuple(A.shape) != (L.FD_NX, L.FD_NX, n) or tuple(B.shape) != (L.FD_NX, L.FD_NU, n):
+        raise ValueError(f"expected A [12][12][n] and B [12][4][n], got {tuple(A.shape)} and {tuple(B.shape)}")
+    check_table(table, n, name, rows)
+    if A.dtype != torch.float64 or B.dtype != torch.float64 or table.dtype != torch.float64:
+        raise ValueError(f"A, B and {name} must be float64")
+    return n
+
+
 @dataclass
-class TrimResult:
+class TrimResult(StatusResult):
+    STATUS_BITS = STATUS_BITS
+    FAILURE = "have no flyable equilibrium at the requested condition"
+
     x0: torch.Tensor            # [12][n] float64: the equilibrium state (FD_X_* rows)
     u0: torch.Tensor            # [4][n]  float64: elevator, aileron, rudder, throttle as set_controls takes them, NOT clipped
     residual: torch.Tensor      # [n] float64: max |F| at the returned point
     iterations: torch.Tensor    # [n] int32
     status: torch.Tensor        # [n] int32: FD_TRIM_* bits
-
-    @property
-    def n(self) -> int:
-        return int(self.status.shape[0])
-
-    @property
-    def ok(self) -> torch.Tensor:
-        return self.status == 0
 
     @property
     def alpha(self) -> torch.Tensor:
@@ -98,8 +169,8 @@ class TrimResult:
         e, a, r, t = self.u0[:, i].cpu().tolist()
         return ControlSurfaces(elevator=e, aileron=a, rudder=r, throttle=t)
 
-    def count_not_ok(self) -> int:
-        return int((self.status != 0).sum())
+
+describe_status = TrimResult.describe_status                 # 'ok' or the names of the FD_TRIM_* bits set in one status word
 
 
 def _type_tensor(n, type_index, device):
@@ -146,6 +217,13 @@ def linearize_into(x: torch.Tensor, u: torch.Tensor, params: torch.Tensor, type_
     return out
 
 
+def linearize_at_trim(trim_result: TrimResult, params: torch.Tensor, type_index=None, scales=None):
+    """(A, B) of every aircraft at its trim (fdyn_linearize at x0, u0): what design_lqr and design_kalman design on.  params
+    [n_types][FD_NP] on the device; type_index [n] or None; scales as `scale_rows` takes them."""
+    n, dev = trim_result.n, trim_result.x0.device
+    return linearize_into(trim_result.x0, trim_result.u0, params, _type_tensor(n, type_index, dev), scale_rows(n, scales, dev))
+
+
 def trim_fleet(n: int, airspeed, climb_angle=0.0, turn_rate=0.0, altitude=100.0, heading=0.0, types: Sequence = ("rc_plane",),
                type_index=None, scales=None, device=None) -> TrimResult:
     """Trim n aircraft: scalars or length-n arrays per flight-condition word, `types` the airframes and `type_index` [n] which
@@ -174,8 +252,4 @@ def lateral_block(A, B):
 
 def require_ok(result: TrimResult, what: str = "trim"):
     """ValueError naming how many lanes are not a flyable equilibrium, and why for the first of them."""
-    bad = result.count_not_ok()
-    if bad:
-        first = int(torch.nonzero(result.status != 0)[0])
-        raise ValueError(f"{what}: {bad} of {result.n} aircraft have no flyable equilibrium at the requested condition "
-                         f"(first: aircraft {first}: {describe_status(int(result.status[first]))})")
+    result.require_ok(what)

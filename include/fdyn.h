@@ -174,22 +174,31 @@ int fdyn_hybrid_step_f32(int level, float* x, float* pid_state, int32_t* wp_idx,
  *        multiple of FD_EV_SHARDS (FDYN_ERR_BAD_SIZE otherwise); fdyn_event_capacity(n) never drops a record.
  *        ev_count_next [FD_EV_SHARDS] or NULL: a second counter set this launch clears, so two sets can be
  *        ping-ponged across steps without a memset on the stream                                              */
-#define FDYN_DECLARE_ENV(SUFFIX, S, E)                                                                          \
-    int fdyn_rate_env_reset_##SUFFIX(S* x, E* e, int32_t* ei, float* pid_state, const uint8_t* mask,            \
-                                     const double* env_consts, const double* pool, int pool_depth,              \
-                                     uint64_t seed, float* obs_out, int64_t n, void* stream);                   \
-    int fdyn_rate_env_step_##SUFFIX(S* x, E* e, int32_t* ei, const uint8_t* type, const double* params,         \
-                                    int n_types, const double* env_consts, const float* actions,                \
-                                    float* pid_state, const float* pid_cfg, const double* casc_consts,          \
-                                    float* actions_out, const S* rw_delta, const double* pool, int pool_depth,  \
-                                    uint64_t seed, int auto_reset, float residual_scale, float* obs_out,        \
-                                    float* reward_f32,                                                          \
-                                    S* reward_full, uint8_t* terminated, uint8_t* truncated,                    \
-                                    int32_t* ev_count, int32_t* ev_count_next, int32_t* ev_int,                 \
-                                    float* ev_flt, int ev_cap, int64_t n, void* stream);
-FDYN_DECLARE_ENV(f64, double, double)
-FDYN_DECLARE_ENV(mixed, double, float)       /* fp32 env words: see fdyn_layout.h, FD_E_* */
-FDYN_DECLARE_ENV(f32, float, float)
+int fdyn_rate_env_reset_f64(double* x, double* e, int32_t* ei, float* pid_state, const uint8_t* mask, const double* env_consts,
+                            const double* pool, int pool_depth, uint64_t seed, float* obs_out, int64_t n, void* stream);
+int fdyn_rate_env_step_f64(double* x, double* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+                           const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg,
+                           const double* casc_consts, float* actions_out, const double* rw_delta, const double* pool,
+                           int pool_depth, uint64_t seed, int auto_reset, float residual_scale, float* obs_out,
+                           float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated, int32_t* ev_count,
+                           int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, void* stream);
+/* mixed: fp32 env words, see fdyn_layout.h, FD_E_* */
+int fdyn_rate_env_reset_mixed(double* x, float* e, int32_t* ei, float* pid_state, const uint8_t* mask, const double* env_consts,
+                              const double* pool, int pool_depth, uint64_t seed, float* obs_out, int64_t n, void* stream);
+int fdyn_rate_env_step_mixed(double* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+                             const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg,
+                             const double* casc_consts, float* actions_out, const double* rw_delta, const double* pool,
+                             int pool_depth, uint64_t seed, int auto_reset, float residual_scale, float* obs_out,
+                             float* reward_f32, double* reward_full, uint8_t* terminated, uint8_t* truncated, int32_t* ev_count,
+                             int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, void* stream);
+int fdyn_rate_env_reset_f32(float* x, float* e, int32_t* ei, float* pid_state, const uint8_t* mask, const double* env_consts,
+                            const double* pool, int pool_depth, uint64_t seed, float* obs_out, int64_t n, void* stream);
+int fdyn_rate_env_step_f32(float* x, float* e, int32_t* ei, const uint8_t* type, const double* params, int n_types,
+                           const double* env_consts, const float* actions, float* pid_state, const float* pid_cfg,
+                           const double* casc_consts, float* actions_out, const float* rw_delta, const double* pool,
+                           int pool_depth, uint64_t seed, int auto_reset, float residual_scale, float* obs_out,
+                           float* reward_f32, float* reward_full, uint8_t* terminated, uint8_t* truncated, int32_t* ev_count,
+                           int32_t* ev_count_next, int32_t* ev_int, float* ev_flt, int ev_cap, int64_t n, void* stream);
 
 /* ---- rate-control env with domain randomisation (design_docs/06_RL_AGENT_TRAINING.md "Domain Randomization") ------------------
  * The two entry points above plus dr [FD_NDR][n] in the state dtype (FD_DR_* rows) and dr_consts [FD_NDC] fp64 (FD_DC_* ranges);

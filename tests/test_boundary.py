@@ -22,13 +22,7 @@ PKG = os.path.join(REPO, "hybrid-classical-and-reinforcement-learning-aircraft-c
 def _declared_symbols():
     src = open(os.path.join(REPO, "include", "fdyn.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    names = set(re.findall(r"\b(?:int|int64_t)\s+(fdyn_\w+)\s*\(", src))
-    # the env entry points are declared through FDYN_DECLARE_ENV(SUFFIX, S)
-    names = {n for n in names if "##" not in n}
-    for suffix in re.findall(r"FDYN_DECLARE_ENV\((\w+),", src):
-        if suffix != "SUFFIX":
-            names |= {f"fdyn_rate_env_reset_{suffix}", f"fdyn_rate_env_step_{suffix}"}
-    return names
+    return set(re.findall(r"\b(?:int|int64_t)\s+(fdyn_\w+)\s*\(", src))
 
 
 def test_library_exports_every_declared_symbol():
@@ -41,6 +35,63 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/fdyn.h but not exported"
     assert declared == set(_lib.SIGNATURES), "host binding table and header drifted apart"
     assert lib.fdyn_abi_version() == 3
+
+
+_P, _I, _I64, _U64, _D, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double, ctypes.c_float
+
+
+def test_binding_table_is_parsed_from_the_header():
+    """One hand-written expectation per kind of parameter: (void), double, int64_t return and argument, float, uint64_t next to a
+    double, and the longest list (30 entries)."""
+    S = _lib.SIGNATURES
+    assert len(S) == 82
+    assert S["fdyn_abi_version"] == (_I, [])
+    assert S["fdyn_num_substeps"] == (_I, [_D, _D])
+    assert S["fdyn_event_capacity"] == (_I64, [_I64])
+    # rewards, values, episode_starts, last_values, last_dones, gamma, lam, T, N, adv, ret, stream
+    assert S["fdyn_gae"] == (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I64, _P, _P, _P])
+    # x, x0, u0, K, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, F, sigma, xhat, du_prev, seed, step, z, feedback,
+    # err_est, err_meas, chatter, meas_out, stream
+    assert S["fdyn_lqg_step_f32"] == (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _D, _I, _P, _P, _P, _P, _P, _P, _U64, _P, _P, _I,
+                                           _P, _P, _P, _P, _P])
+    # x, e, ei, type, params, n_types, env_consts, actions, pid_state, pid_cfg, casc_consts, actions_out, rw_delta, pool,
+    # pool_depth, seed, auto_reset, residual_scale, obs_out, reward_f32, reward_full, terminated, truncated, ev_count,
+    # ev_count_next, ev_int, ev_flt, ev_cap, n, stream
+    assert S["fdyn_rate_env_step_mixed"] == (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _U64, _I, _F, _P, _P,
+                                                  _P, _P, _P, _P, _P, _P, _P, _I, _I64, _P])
+    assert len(S["fdyn_rate_env_step_mixed"][1]) == 30
+
+
+def test_header_parser_is_strict():
+    table, consts = _lib._parse_header("""
+        /* int fdyn_in_a_comment(int a);
+           #define FDYN_IN_A_COMMENT 7 */
+        // int fdyn_in_a_line_comment(int a);
+        #define FDYN_SOME_CODE (-5)   /* a code */
+        #define FDYN_MACRO(S) \\
+            int fdyn_in_a_macro_##S(int a);
+        int64_t fdyn_a(const double* x /*host*/, int64_t n, uint64_t seed, float g,
+                       double dt, const int k, void* stream);
+        int fdyn_b(void);
+    """)
+    assert table == {"fdyn_a": (_I64, [_P, _I64, _U64, _F, _D, _I, _P]), "fdyn_b": (_I, [])}
+    assert consts == {"FDYN_SOME_CODE": -5}
+    with pytest.raises(ValueError, match=r"fdyn_c.*'unsigned n'"):
+        _lib._parse_header("int fdyn_c(void* p, unsigned n);")
+    with pytest.raises(ValueError, match=r"fdyn_c.*'size_t n'"):
+        _lib._parse_header("int fdyn_c(size_t n);")
+    with pytest.raises(ValueError, match="fdyn_d"):                          # a return type the table has no restype for
+        _lib._parse_header("int fdyn_b(void);\nvoid fdyn_d(int a);")
+    with pytest.raises(ValueError, match="fdyn_e"):
+        _lib._parse_header("int fdyn_e(int (*callback)(int), int n);")
+    with pytest.raises(ValueError, match="fdyn_b"):                          # one name, two declarations
+        _lib._parse_header("int fdyn_b(void);\nint fdyn_b(int a);")
+
+
+def test_return_codes_and_abi_version_come_from_the_header():
+    assert (_lib.FDYN_OK, _lib.FDYN_ERR_BAD_DT, _lib.FDYN_ERR_BAD_TYPES, _lib.FDYN_ERR_BAD_SIZE, _lib.FDYN_ERR_NULL) == (0, -1, -2, -3, -4)
+    src = open(os.path.join(REPO, "include", "fdyn.h")).read()
+    assert _lib.FDYN_ABI_VERSION == int(re.search(r"#define\s+FDYN_ABI_VERSION\s+(\d+)", src).group(1))
 
 
 def test_code_object_is_gfx950():
