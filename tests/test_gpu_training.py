@@ -723,6 +723,7 @@ def test_policy_features_kernel_matches_plain_torch_fp32(B):
     and against the layer-wise device path it replaces.  Random weights with non-zero biases and an asymmetric observation
     batch: a wrong k permutation, fragment order or gate offset cannot pass."""
     from hcrl_amd import _lib
+    from hcrl_amd.inference import mlp_bf16
     from hcrl_amd.policy import FE_GATE_SCALE
     lib = _lib.load()
     torch.manual_seed(11)
@@ -735,7 +736,7 @@ def test_policy_features_kernel_matches_plain_torch_fp32(B):
     inf = p._inf
     obs = torch.randn(B, 18, device="cuda") * torch.linspace(0.2, 2.0, 18, device="cuda")
     feats = torch.empty((B, 128), dtype=torch.bfloat16, device="cuda")
-    _lib.check(lib.fdyn_policy_features(obs.data_ptr(), inf["fe_img"].data_ptr(), inf["fe_bias"].data_ptr(), feats.data_ptr(), B,
+    _lib.check(lib.fdyn_policy_features(obs.data_ptr(), inf.fe_img.data_ptr(), inf.fe_bias.data_ptr(), feats.data_ptr(), B,
                                         _lib.current_stream()), "policy_features")
     torch.cuda.synchronize()
     bf = lambda t: t.to(torch.bfloat16).float()      # noqa: E731
@@ -756,13 +757,13 @@ def test_policy_features_kernel_matches_plain_torch_fp32(B):
         st = p.initial_state(B, "cuda")
         keep = torch.ones(B, device="cuda")
         with torch.no_grad():
-            x2 = p._mlp_bf16(obs.to(torch.bfloat16), inf["emb"])
-            for w, b in zip(inf["fe_w"], inf["fe_b"]):
+            x2 = mlp_bf16(obs.to(torch.bfloat16), inf.emb)
+            for w, b in zip(inf.fe_w, inf.fe_b):
                 h = torch.empty((B, 256), dtype=torch.bfloat16, device="cuda")
                 _lib.check(lib.fdyn_lstm_cell_mfma(x2.data_ptr(), x2.shape[1], None, 0, None, None, w.data_ptr(), b.data_ptr(),
                                                    h.data_ptr(), None, None, B, 256, _lib.current_stream()), "cell")
                 x2 = h
-            layerwise = p._mlp_bf16(x2, inf["proj"])
+            layerwise = mlp_bf16(x2, inf.proj)
     finally:
         del os.environ["FDYN_NO_FE64"]
     assert (feats.float() - layerwise.float()).abs().max().item() < 3e-2 * max(1.0, ref.abs().max().item())
@@ -967,3 +968,78 @@ def test_done_flags_inside_the_policy_step_equal_the_glue_launch(B):
     done = ((term | trunc) != 0).float()
     assert c1 == 8 and int(ctr) == 8 and torch.equal(es0, done) and torch.equal(kp0, 1.0 - done) and torch.equal(es0, es1)
     assert torch.equal(a1, a0) and torch.equal(v1, v0) and torch.equal(lp1, lp0) and all(torch.equal(x, y) for x, y in zip(s1, s0))
+
+
+def _random_state(p, B):
+    """Non-zero recurrent state in the fused path's own dtypes (h bf16, c fp32)."""
+    from hcrl_amd.policy import RNNStates
+    return RNNStates(*(torch.randn(B, p.hidden, device="cuda").to(dt) * 0.5 for dt in (torch.bfloat16, torch.float32) * 2))
+
+
+@pytest.mark.parametrize("B", [512, 32768])
+def test_two_cell_launches_through_the_policy_step_equal_the_paired_launch(B, monkeypatch):
+    """policy.step with FDYN_NO_CELL_PAIR=1 (actor and critic cell as two calls of fdyn_lstm_cell_mfma) against the default route
+    (fdyn_lstm_cell_mfma_pair): 512 rows run the tiled cell behind the layer-wise features, 32 768 the one-wave-per-SIMD cell
+    behind the one-kernel features.  The two forms are the same kernel on the same operands
+    (test_cell_pair_in_one_launch_equals_two_launches), so everything downstream is equal bit for bit."""
+    torch.manual_seed(21)
+    p = RateLSTMPolicy(compute_dtype=torch.bfloat16).cuda()
+    with torch.no_grad():
+        p.action_net.weight.mul_(30.0)
+    p.prepare_inference()
+    obs, st = torch.randn(B, 18, device="cuda"), _random_state(p, B)
+    start = (torch.rand(B, device="cuda") < 0.05).float()
+    with torch.no_grad():
+        assert p._fused_ok(obs)
+        a1, v1, _, s1 = p.step(obs, st, start, deterministic=True, bump_noise=False)
+        monkeypatch.setenv("FDYN_NO_CELL_PAIR", "1")
+        a0, v0, _, s0 = p.step(obs, st, start, deterministic=True, bump_noise=False)
+    assert a1.shape == (B, 4) and float(a1.abs().max()) > 0.1 and not torch.equal(s1.pi_h, st.pi_h)
+    assert torch.equal(a1, a0) and torch.equal(v1, v0) and all(torch.equal(x, y) for x, y in zip(s1, s0))
+
+
+def test_policy_the_heads_kernels_do_not_serve_takes_the_plain_path(monkeypatch):
+    """net_arch_pi=(128, 32): action_net is [4, 32], which no heads kernel reads.  The policy gets no inference snapshot and
+    steps on the plain autocast path -- the path FDYN_NO_MFMA=1 selects -- instead of failing inside the fused one."""
+    torch.manual_seed(22)
+    B = 300
+    p = RateLSTMPolicy(net_arch_pi=(128, 32), compute_dtype=torch.bfloat16).cuda()
+    p.prepare_inference()
+    obs, st = torch.randn(B, 18, device="cuda"), _random_state(p, B)
+    start = (torch.rand(B, device="cuda") < 0.05).float()
+    with torch.no_grad():
+        assert p._inf is None and not p._fused_ok(obs)
+        a1, v1, lp1, s1 = p.step(obs, st, start, deterministic=True)
+        monkeypatch.setenv("FDYN_NO_MFMA", "1")
+        a0, v0, lp0, s0 = p.step(obs, st, start, deterministic=True)
+    assert a1.shape == (B, 4) and v1.shape == (B,) and lp1.shape == (B,) and all(t.shape == (B, 256) for t in s1)
+    assert all(bool(torch.isfinite(t.float()).all()) for t in (a1, v1, lp1, *s1))
+    assert torch.equal(a1, a0) and torch.equal(v1, v0) and torch.equal(lp1, lp0) and all(torch.equal(x, y) for x, y in zip(s1, s0))
+
+
+def test_gemm_trunks_match_the_trunk_kernel(monkeypatch):
+    """FDYN_NO_TRUNK=1 (each trunk as two hipBLASLt GEMMs with bias + ReLU epilogues, then fdyn_policy_heads: what every trunk
+    of another shape than [256 -> 128 -> 64] runs) against FDYN_NO_TRUNK_HEADS=1 (fdyn_policy_trunks, then the same
+    fdyn_policy_heads), 300 rows: tail rows in both.  Both forms round each trunk layer's output to bf16 once; where their fp32
+    sums differ in the last bits the rounded outputs may or may not.  Measured with this seed on the commit before inference.py
+    existed, where both routes ran from policy.py untouched (profiles/inference_routes_ab.txt): max |d actions| = 0 against max
+    |actions| 0.122, max |d values| = 0 against max |values| 0.315, and the same on this tree -- so the bound is equality."""
+    torch.manual_seed(23)
+    B = 300
+    p = RateLSTMPolicy(compute_dtype=torch.bfloat16).cuda()
+    with torch.no_grad():
+        p.action_net.weight.mul_(30.0)                      # the 0.01-gain initialisation would leave the means ~0: make them visible
+    p.prepare_inference()
+    obs, st = torch.randn(B, 18, device="cuda"), _random_state(p, B)
+    start = (torch.rand(B, device="cuda") < 0.05).float()
+    with torch.no_grad():
+        monkeypatch.setenv("FDYN_NO_TRUNK", "1")
+        a0, v0, _, s0 = p.step(obs, st, start, deterministic=True, bump_noise=False)
+        monkeypatch.delenv("FDYN_NO_TRUNK")
+        monkeypatch.setenv("FDYN_NO_TRUNK_HEADS", "1")
+        a1, v1, _, s1 = p.step(obs, st, start, deterministic=True, bump_noise=False)
+    da, dv = float((a1 - a0).abs().max()), float((v1 - v0).abs().max())
+    print(f"GEMM trunks against the trunk kernel: max |d actions| {da:.3e} (max |actions| {float(a1.abs().max()):.3f}), "
+          f"max |d values| {dv:.3e} (max |values| {float(v1.abs().max()):.3f})")
+    assert all(torch.equal(x, y) for x, y in zip(s1, s0)) and float(a1.abs().max()) > 0.1
+    assert torch.equal(a1, a0) and torch.equal(v1, v0)
