@@ -12,8 +12,8 @@ LIB_PATH = os.environ.get("FDYN_LIB", os.path.join(_HERE, "csrc", "libfdyn_hip.s
 _SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "float": C.c_float}
 
 
-def _parse_header(src):
-    """The text of include/fdyn.h -> ({name: (restype, [argtypes])} of every fdyn_* prototype, {name: value} of every integer
+def _parse_header(src, header="include/fdyn.h"):
+    """The text of include/fdyn.h (or of `header`, named in the errors) -> ({name: (restype, [argtypes])} of every fdyn_* prototype, {name: value} of every integer
     `#define FDYN_*`).  Strict: a parameter or a declaration it cannot type is a ValueError, never a guess."""
     src = re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
     consts = {name: int(val) for name, val in re.findall(r"^[ \t]*#define[ \t]+(FDYN_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", src, flags=re.M)}
@@ -29,11 +29,11 @@ def _parse_header(src):
             elif len(scalar) == 1 and scalar[0] in _SCALARS:
                 args.append(_SCALARS[scalar[0]])
             else:
-                raise ValueError(f"include/fdyn.h: {name}: no ctypes type for the parameter '{param.strip()}'")
+                raise ValueError(f"{header}: {name}: no ctypes type for the parameter '{param.strip()}'")
         table[name] = (_SCALARS[res], args)
     heads = re.findall(r"\b(fdyn_\w+)\s*\(", src)
     if len(heads) != len(table):                 # another return type, a function pointer, a name declared twice
-        raise ValueError(f"include/fdyn.h: {len(heads)} fdyn_* prototype heads, {len(table)} parsed; look at "
+        raise ValueError(f"{header}: {len(heads)} fdyn_* prototype heads, {len(table)} parsed; look at "
                          f"{sorted(set(heads) - set(table)) or sorted(h for h in set(heads) if heads.count(h) > 1)}")
     return table, consts
 
@@ -44,6 +44,10 @@ def _parse_header(src):
 with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn.h")) as _f:
     SIGNATURES, _CONSTS = _parse_header(_f.read())
 globals().update(_CONSTS)
+# the flight-mode report has a header of its own (include/fdyn_modes.h), in the same prototype style: a second table, bound to the
+# same library
+with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_modes.h")) as _f:
+    MODES_SIGNATURES = _parse_header(_f.read(), "include/fdyn_modes.h")[0]
 
 _lib = None
 
@@ -60,7 +64,7 @@ def load():
             raise FdynError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(hipcc --offload-arch=gfx950). The batched flight-dynamics path has no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *MODES_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
         if lib.fdyn_abi_version() != FDYN_ABI_VERSION:

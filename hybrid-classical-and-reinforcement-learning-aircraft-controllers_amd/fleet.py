@@ -162,6 +162,15 @@ class BatchedSixDOF:
         from . import margins as M
         return M.loop_margins(*self._need_designs("loop_margins"), feedback, omega, curve)
 
+    # Flight modes (hcrl_amd.modes): where the poles are
+    def modes(self, design=None, scales=None):
+        """FleetModes of every aircraft linearised at the fleet's current trim (the last `.trim(...)`): the open-loop poles, or
+        with `design` (an LqrDesign) those of a - b K; eig [2][4][N] (longitudinal | lateral), summary [2][FD_NMO][N].  scales:
+        None = the multipliers the trim was solved with.  The fleet's state is not touched."""
+        from . import modes as MO
+        res, trim_scales = self._need_trim("modes")
+        return MO.fleet_modes(res, self.params, self.type_index, trim_scales if scales is None else scales, design)
+
     def _need_trim(self, what: str):
         if self._trim is None:
             raise ValueError(f"{type(self).__name__}.{what}: the fleet has no trim; call .trim(...) first")

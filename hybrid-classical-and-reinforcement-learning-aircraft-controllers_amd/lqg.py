@@ -99,6 +99,11 @@ class KalmanDesign(T.StatusResult):
         eye = torch.eye(4, dtype=self.F.dtype, device=self.F.device)[None, :, :, None]
         return torch.einsum("bikn,bkjn->bijn", self.phi(), eye - self.gain())
 
+    def filter_poles(self):
+        """FleetModes of Phi (I - L) (one launch of fdyn_block_modes): spectral_radius() [2][n] < 1 is the filter's stability."""
+        from . import modes as MO
+        return MO.block_modes_into(self.filter_matrix())
+
 
 describe_status = KalmanDesign.describe_status               # 'ok' or the names of the FD_KF_* bits set in one status word
 

@@ -96,6 +96,12 @@ class LqrDesign(T.StatusResult):
         """A - B K [12][12][n] on the device."""
         return A - torch.einsum("ikn,kjn->ijn", B, self.gain_matrix())
 
+    def modes(self, A: torch.Tensor, B: torch.Tensor):
+        """FleetModes of a - b K per block (one launch of fdyn_flight_modes): the closed-loop poles of the model A, B under these
+        gains."""
+        from . import modes as MO
+        return MO.modes_into(A, B, self.K)
+
 
 describe_status = LqrDesign.describe_status                  # 'ok' or the names of the FD_LQR_* bits set in one status word
 
@@ -120,6 +126,16 @@ def design_lqr(trim_result, params: torch.Tensor, type_index=None, scales=None, 
     out = lqr_into(A, B, weights_tensor(weights, trim_result.n, A.device))
     out.x0, out.u0 = trim_result.x0, trim_result.u0
     return out
+
+
+def sampled_poles(design: LqrDesign, kalman):
+    """FleetModes of Phi - Gamma Kb per block: the poles of the state-feedback loop as fdyn_lqr_step_* flies it at the step
+    `kalman` (a KalmanDesign) was discretised at, composed on the device; spectral_radius() < 1 = Schur."""
+    from . import modes as MO
+    if design.n != kalman.n:
+        raise ValueError(f"the LQR design has {design.n} aircraft, the Kalman design {kalman.n}")
+    Kb = torch.stack([design.K[base:base + 8].reshape(2, 4, design.n) for base in (L.FD_LQK_LON, L.FD_LQK_LAT)])
+    return MO.block_modes_into(kalman.phi() - torch.einsum("bikn,bkjn->bijn", kalman.gamma(), Kb))
 
 
 def require_ok(design: LqrDesign, what: str = "design_lqr"):

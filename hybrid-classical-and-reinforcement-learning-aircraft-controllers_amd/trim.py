@@ -40,7 +40,7 @@ def status_names(bits, status: int) -> str:
 
 
 class StatusResult:
-    """What TrimResult, LqrDesign, KalmanDesign and LoopMargins share: the reading of their `status` [n] int32.  A subclass names
+    """What TrimResult, LqrDesign, KalmanDesign, LoopMargins and FleetModes share: the reading of their `status` [n] int32.  A subclass names
     its module's STATUS_BITS and, where it has a strict check, what its failed lanes lack (FAILURE)."""
     STATUS_BITS = ()
     FAILURE = "have a non-zero status"

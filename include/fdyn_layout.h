@@ -296,6 +296,17 @@ enum { FD_LQG_ESTIMATE = 0, FD_LQG_MEASUREMENT = 1, FD_LQG_TRUTH = 2 };
  *   BAD_INPUT   a word of K or F that is read is not finite: nothing was computed, the outputs as for SINGULAR               */
 enum { FD_MRG_NOT_STABLE = 1, FD_MRG_SINGULAR = 2, FD_MRG_BAD_INPUT = 4 };
 
+/* ---- flight modes (fdyn_flight_modes / fdyn_block_modes, csrc/modes_kernels.hip, include/fdyn_modes.h) ---------------- */
+/* summary [2][FD_NMO][n] fp64, per block over its four eigenvalues: max Re, max |.| (the spectral radius), min |.|, the
+ * smallest damping ratio -Re / |.| (0 for an eigenvalue at 0; 1 = real and stable, -1 = real and unstable), the number with
+ * Re > 0 and the number with Im != 0 (both as fp64)                                                                    */
+enum { FD_MO_ABSCISSA = 0, FD_MO_RADIUS, FD_MO_MIN_ABS, FD_MO_MIN_ZETA, FD_MO_N_UNSTABLE, FD_MO_N_COMPLEX, FD_NMO = 6 };
+/* status of a modes report (values, not bits); 0 = every eigenvalue of both blocks converged
+ *   NOT_CONVERGED  a deflation hit its cap of 30 QR sweeps or a word stopped being finite
+ *   BAD_INPUT      a word of a block that is read (A, and B and K where K is given; M) is not finite: nothing was solved
+ * either way every eigenvalue and summary word of BOTH blocks of the lane is NaN                                          */
+enum { FD_MO_NOT_CONVERGED = 1, FD_MO_BAD_INPUT = 2 };
+
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
 enum {
