@@ -63,6 +63,13 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise FdynError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(hipcc --offload-arch=gfx950). The batched flight-dynamics path has no CPU fallback.")
+        # the framework's GPU context first.  Observed, cause inside the runtime not established: a process that loads this
+        # library BEFORE torch has initialised the GPU (build() followed by smoke(), the README's command) gets hipErrorNoDevice
+        # (100) from every launch of the library while torch's own kernels run; torch first, every launch works
+        # (tests/test_gpu_launch_image.py: test_library_loaded_before_the_first_gpu_call_still_launches)
+        import torch
+        if torch.cuda.is_available():
+            torch.cuda.init()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *MODES_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = header/library drift

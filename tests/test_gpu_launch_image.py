@@ -125,3 +125,26 @@ def test_image_follows_env_consts_and_params():
     a.step_device(act); c.step_device(act)
     _same(a.x, c.x, "x after a parameter change", 0)
     assert a._image.fills == 3
+
+
+def test_library_loaded_before_the_first_gpu_call_still_launches():
+    """A fresh process that loads the HIP library BEFORE the framework has touched the GPU (what build() followed by smoke() does)
+    fills a launch image and steps: loaded ahead of the runtime's start-up, every launch of the library returned
+    hipErrorNoDevice while the framework's own kernels ran."""
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import hcrl_amd, torch\n"
+            "from hcrl_amd import _lib\n"
+            "assert not torch.cuda.is_initialized()\n"
+            "_lib.load()\n"
+            "from hcrl_amd.rate_env import GpuRateVecEnv\n"
+            "env = GpuRateVecEnv(256, 'medium', 10.0, 0.02, 'step', seed=0, precision='f64', sampling='device')\n"
+            "env.reset()\n"
+            "env.step_device(torch.zeros(256, 4, device=env.device), auto_reset=False)\n"
+            "torch.cuda.synchronize()\n"
+            "assert bool(torch.isfinite(env.x).all())\n"
+            "print('ok')\n")
+    proc = subprocess.run([sys.executable, "-c", code], cwd=repo, capture_output=True, text=True, timeout=120)
+    assert proc.returncode == 0 and proc.stdout.strip().endswith("ok"), proc.stderr[-2000:]
