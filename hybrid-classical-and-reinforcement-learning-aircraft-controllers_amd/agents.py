@@ -373,3 +373,58 @@ class LQRAgent:
 
     def __repr__(self) -> str:
         return "LQRAgent(level=SURFACE)"
+
+
+class LQServoAgent:
+    """The LQ servo (hcrl_amd.servo) for one aircraft, with the reference agents' surface: it enters at the HSA level and takes
+    `ControlCommand(mode=HSA, heading=, speed=, altitude=)`.  The controls come from fdyn_servo_step_f64 with n_steps = 0, the law
+    the fleets fly; the integrators and the moving references then advance by `dt` through one step of the same kernel on a copy
+    of the state that is thrown away, so the agent's words stay bit-identical to a fleet lane's.  `design` is a ServoDesign with
+    its trim point (lane `lane` is taken); `limits` are the error clips."""
+    MODE = ControlMode.HSA
+
+    def __init__(self, design, lane: int = 0, limits=None):
+        from . import servo as SV
+        if design.x0 is None or design.u0 is None:
+            raise ValueError("LQServoAgent needs a design that carries its trim point (x0, u0)")
+        self._fleet = BatchedSixDOF(1, "f64")
+        dev = self._fleet.device
+        one = lambda t: t[..., lane:lane + 1].to(dev).contiguous()   # noqa: E731
+        self._design = SV.ServoDesign(one(design.K), one(design.residual), one(design.iterations), one(design.status),
+                                      one(design.x0), one(design.u0))
+        self._limits = SV.DEFAULT_LIMITS if limits is None else limits
+        self._scratch = torch.empty_like(self._fleet.x)
+        self.reset()
+
+    def get_control_level(self) -> ControlMode:
+        return ControlMode.HSA
+
+    @property
+    def state(self):
+        """The ServoState of the one aircraft: references, integrators, last errors."""
+        return self._state
+
+    def compute_action(self, command, state: AircraftState, dt: Optional[float] = None) -> ControlSurfaces:
+        """`command`: a ControlCommand in HSA mode whose heading (rad), speed (m/s) and altitude (m) become the references (a
+        field left None keeps the reference it had), or None to keep all of them."""
+        from . import servo as SV
+        if command is not None:
+            if command.mode != ControlMode.HSA:
+                raise ValueError(f"LQServoAgent takes HSA commands, got {command.mode}")
+            self._state.command(heading=command.heading, speed=command.speed, altitude=command.altitude)
+        f, dt = self._fleet, 0.01 if dt is None else dt
+        f.x.copy_(torch.as_tensor(state.to_vector(), device=f.device).reshape(L.FD_NX, 1))
+        SV.step_into("f64", f.x, self._design, self._state, f.params, None, dt, 0, f.u)
+        self._scratch.copy_(f.x)
+        SV.step_into("f64", self._scratch, self._design, self._state, f.params, None, dt, 1, None, None, self._state.err)
+        s = f.u[:, 0].cpu().numpy()
+        return ControlSurfaces(elevator=float(s[L.FD_U_ELEVATOR]), aileron=float(s[L.FD_U_AILERON]),
+                               rudder=float(s[L.FD_U_RUDDER]), throttle=float(s[L.FD_U_THROTTLE]))
+
+    def reset(self):
+        """References back to the trim's own airspeed, altitude, heading and rates; integrators to zero."""
+        from . import servo as SV
+        self._state = SV.ServoState.at_trim(self._design.x0, self._limits)
+
+    def __repr__(self) -> str:
+        return "LQServoAgent(level=HSA)"

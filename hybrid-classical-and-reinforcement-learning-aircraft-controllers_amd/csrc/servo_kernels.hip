@@ -1,0 +1,370 @@
+// servo_kernels.hip -- LQ servo for whole fleets, gfx950: LQR with integral action on airspeed, altitude and heading, so that a
+// fleet designed at a trim can be told to climb, turn and change speed (include/fdyn_servo.h).
+//
+// fdyn_servo_design   each aircraft's own A, B (fdyn_linearize) and trim x0 are cut into the augmented longitudinal block
+//                     (u, w, q, theta, z, i_V, i_h | elevator, throttle) and the augmented lateral block (v, p, r, phi, psi, i_psi |
+//                     aileron, rudder); each block's continuous Riccati equation is solved in fp64, one lane per aircraft, by
+//                     fdyn_riccati_n.hpp (the 4 x 4 solver of lqr_kernels.hip at N = 7 and N = 6): K = R^-1 b^T X per block.
+// fdyn_servo_step_*   n_steps x { errors against the references -> u = u0 - K d -> Controls::set (clips as set_controls does) ->
+//                     integrators, frozen per block while one of its controls is clipped -> one RK4 of dt -> the references move
+//                     at their own rates }, one launch, through the steppers of fdyn_core.hpp exactly as lqr_step_kernel calls them.
+//
+// Design: two 7 x 7 / 6 x 6 solves in fp64 do not fit the register file; the matrices the compiler cannot keep go to scratch.  The
+// kernel runs once per design, 64-lane workgroups.
+// Step: the lane's law (26 gains, the trim point, references, integrators) does not fit beside the fp64 physics either: the words
+// live in LDS as [word][lane] columns of 64-lane workgroups, as lqg_step_kernel keeps its filter; a lane reads and writes its
+// own column only, so no barrier follows the staging one.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "fdyn_fleet.hpp"
+#include "fdyn_riccati_n.hpp"
+#include "../../include/fdyn_servo.h"
+
+using namespace fdyn;
+
+namespace {
+
+constexpr int TB = 64;                   // design: threads per workgroup
+constexpr int LB = 64;                   // step: threads per workgroup (what the LDS columns allow)
+constexpr int NLON = FD_SV_NLON, NLAT = FD_SV_NLAT;
+
+// the rows / columns of A and B a block reads: the first five states of each block
+__device__ constexpr int LON_W[5] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_D };
+__device__ constexpr int LAT_W[5] = { FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL, FD_X_YAW };
+
+// the 5 x 5 part of an augmented block and its two control columns; everything else of a, b is zero.  False when a word is not finite.
+template <int N>
+FD_DEV bool load_block(const double* __restrict__ A, const double* __restrict__ B, int64_t n, int64_t i, const int (&sr)[5], int c0, int c1,
+                       MN<N>& a, double (&b)[N][2])
+{
+    bool fin = true;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) a.v[r][c] = 0.0;
+        b[r][0] = b[r][1] = 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) { a.v[r][c] = A[int64_t(sr[r] * FD_NX + sr[c]) * n + i]; fin = fin && ::isfinite(a.v[r][c]); }
+        b[r][0] = B[int64_t(sr[r] * FD_NU + c0) * n + i];
+        b[r][1] = B[int64_t(sr[r] * FD_NU + c1) * n + i];
+        fin = fin && ::isfinite(b[r][0]) && ::isfinite(b[r][1]);
+    }
+    return fin;
+}
+
+__global__ void __launch_bounds__(TB)
+servo_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __restrict__ B /*[48][n]*/, const double* __restrict__ x0 /*[12][n]*/,
+                    const double* __restrict__ weights /*[17] or [17][n]*/, int weights_per_lane, int64_t n,
+                    double* __restrict__ K /*[26][n]*/, double* __restrict__ residual, int32_t* __restrict__ iters,
+                    int32_t* __restrict__ status)
+{
+#pragma clang fp contract(off)
+    const int64_t i = int64_t(blockIdx.x) * TB + threadIdx.x;
+    if (i >= n) return;
+    double w[FD_NSVW];
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < FD_NSVW; ++k) {
+        w[k] = weights_per_lane ? weights[k * n + i] : weights[k];
+        bad = bad || !(::isfinite(w[k]) && w[k] > 0.0);
+    }
+    const double u0 = x0[FD_X_U * n + i], w0 = x0[FD_X_W * n + i];
+    const double V0 = ::sqrt(u0 * u0 + w0 * w0);
+    bad = bad || !(::isfinite(u0) && ::isfinite(w0) && V0 > 0.0);
+
+    double Kall[FD_NSVK];
+#pragma unroll
+    for (int k = 0; k < FD_NSVK; ++k) Kall[k] = 0.0;
+    double res = 0.0;
+    int it_max = 0, st = 0;
+
+    {   // longitudinal: (u, w, q, theta, z) of A, then i_V' = (u0 du + w0 dw) / V0 and i_h' = -dz
+        MN<NLON> a;
+        double b[NLON][2], q[NLON], rinv[2];
+        bad = !load_block<NLON>(A, B, n, i, LON_W, FD_U_ELEVATOR, FD_U_THROTTLE, a, b) || bad;
+        a.v[5][0] = u0 / V0;
+        a.v[5][1] = w0 / V0;
+        a.v[6][4] = -1.0;
+#pragma unroll
+        for (int r = 0; r < NLON; ++r) q[r] = w[FD_SVW_Q_LON + r];
+        rinv[0] = 1.0 / w[FD_SVW_R_LON];
+        rinv[1] = 1.0 / w[FD_SVW_R_LON + 1];
+        // the lateral block's words are read before anything is solved: BAD_INPUT (weights, trim, either block) solves nothing
+        {
+            bool fin = true;
+#pragma unroll
+            for (int r = 0; r < 5; ++r) {
+#pragma unroll
+                for (int c = 0; c < 5; ++c) fin = fin && ::isfinite(A[int64_t(LAT_W[r] * FD_NX + LAT_W[c]) * n + i]);
+                fin = fin && ::isfinite(B[int64_t(LAT_W[r] * FD_NU + FD_U_AILERON) * n + i]) && ::isfinite(B[int64_t(LAT_W[r] * FD_NU + FD_U_RUDDER) * n + i]);
+            }
+            bad = bad || !fin;
+        }
+        if (!bad) {
+            CareResult<NLON> r;
+            care_solve<NLON>(a, b, q, rinv, r);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int c = 0; c < NLON; ++c) Kall[FD_SVK_LON + j * NLON + c] = r.K[j][c];
+            res = nan_max(res, r.residual);
+            it_max = r.iters > it_max ? r.iters : it_max;
+            if (r.failed || !r.converged) st |= FD_SV_NOT_CONVERGED;
+            if (!r.positive || !(r.residual <= RIC_RES_MAX)) st |= FD_SV_NO_CERTIFICATE;
+        }
+    }
+    if (!bad) {   // lateral: (v, p, r, phi, psi) of A, then i_psi' = dpsi
+        MN<NLAT> a;
+        double b[NLAT][2], q[NLAT], rinv[2];
+        load_block<NLAT>(A, B, n, i, LAT_W, FD_U_AILERON, FD_U_RUDDER, a, b);
+        a.v[5][4] = 1.0;
+#pragma unroll
+        for (int r = 0; r < NLAT; ++r) q[r] = w[FD_SVW_Q_LAT + r];
+        rinv[0] = 1.0 / w[FD_SVW_R_LAT];
+        rinv[1] = 1.0 / w[FD_SVW_R_LAT + 1];
+        CareResult<NLAT> r;
+        care_solve<NLAT>(a, b, q, rinv, r);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int c = 0; c < NLAT; ++c) Kall[FD_SVK_LAT + j * NLAT + c] = r.K[j][c];
+        res = nan_max(res, r.residual);
+        it_max = r.iters > it_max ? r.iters : it_max;
+        if (r.failed || !r.converged) st |= FD_SV_NOT_CONVERGED;
+        if (!r.positive || !(r.residual <= RIC_RES_MAX)) st |= FD_SV_NO_CERTIFICATE;
+    }
+
+    if (bad) { st = FD_SV_BAD_INPUT; res = __builtin_nan(""); it_max = 0; }
+#pragma unroll
+    for (int k = 0; k < FD_NSVK; ++k) K[k * n + i] = st ? 0.0 : Kall[k];
+    residual[i] = res;
+    iters[i] = it_max;
+    status[i] = st;
+}
+
+// ---- the closed loop ------------------------------------------------------------------------------------------------------------
+// One lane's column of [word][lane] LDS words.
+template <typename W> struct Column {
+    W* col;
+    FD_DEV explicit Column(W* lds) : col(lds + threadIdx.x) {}
+    FD_DEV W get(int k) const { return col[k * LB]; }
+    FD_DEV void set(int k, W v) { col[k * LB] = v; }
+};
+// fp64 words: the eight regulated words of the trim (LqrLaw's order), its airspeed V0, then the references
+enum { SD_X0 = 0, SD_V0 = 8, SD_REF = 9, SD_N = SD_REF + FD_NSVR };
+// glue-type words: the gains, u0, the direction (u0, w0) / V0 of the trim's velocity, the integrators
+enum { SG_K = 0, SG_U0 = FD_NSVK, SG_CU = SG_U0 + FD_NU, SG_CW, SG_INT, SG_N = SG_INT + FD_NSVI };
+
+template <typename G> FD_DEV bool outside(G v, G lo, G hi) { return !(v >= lo && v <= hi); }     // true for NaN, as any_clipped
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_step_kernel(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,
+                  const double* __restrict__ K /*[26][n]*/, double* __restrict__ ref /*[5][n]*/, double* __restrict__ integ /*[3][n]*/,
+                  const double* __restrict__ limits /*[3]*/, const uint8_t* __restrict__ type, const double* __restrict__ params,
+                  int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out /*[4][n]*/, int32_t* __restrict__ sat_steps,
+                  double* __restrict__ err_out /*[3][n]*/)
+{
+    using G = typename GlueOf<S, T>::type;
+    constexpr bool FAST = sizeof(T) == 4;
+    __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
+    __shared__ double s_d[SD_N * LB];
+    __shared__ G s_g[SG_N * LB];
+    stage_params<FAST>(s_params, params, n_types);
+    __syncthreads();
+    const int64_t i = int64_t(blockIdx.x) * LB + threadIdx.x;
+    if (i >= n) return;
+    Column<double> ld(s_d);
+    Column<G> lg(s_g);
+    {
+#pragma clang fp contract(off)
+        constexpr int W[8] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL };
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ld.set(SD_X0 + j, x0[W[j] * n + i]);
+        const double tu = x0[FD_X_U * n + i], tw = x0[FD_X_W * n + i];
+        const double V0 = ::sqrt(tu * tu + tw * tw);
+        const bool moving = V0 > 0.0;                            // false only for a lane whose design was refused (K = 0)
+        ld.set(SD_V0, V0);
+        lg.set(SG_CU, G(moving ? tu / V0 : 0.0));
+        lg.set(SG_CW, G(moving ? tw / V0 : 0.0));
+#pragma unroll
+        for (int k = 0; k < FD_NSVR; ++k) ld.set(SD_REF + k, ref[int64_t(k) * n + i]);
+#pragma unroll
+        for (int k = 0; k < FD_NSVK; ++k) lg.set(SG_K + k, G(K[int64_t(k) * n + i]));
+#pragma unroll
+        for (int k = 0; k < FD_NU; ++k) lg.set(SG_U0 + k, G(u0[int64_t(k) * n + i]));
+#pragma unroll
+        for (int k = 0; k < FD_NSVI; ++k) lg.set(SG_INT + k, G(integ[int64_t(k) * n + i]));
+    }
+    S x[FD_NX];
+#pragma unroll
+    for (int k = 0; k < FD_NX; ++k) x[k] = xs[k * n + i];
+    asm volatile("" ::: "memory");
+    const double* blk = s_params + lane_type(type, i, n_types) * FD_NP_STAGED;
+    Params<T> P; P.load(blk);
+    Limits<S> Lm; Lm.load(blk);
+    Surfaces<G> surf{ G(0), G(0), G(0), G(0) };
+    G err[FD_NSVI] = { G(0), G(0), G(0) };
+    int sat = 0;
+
+    // one control step up to the integrators: returns the unclipped controls (Controls::set clips).  `advance` is false for the
+    // controls-only call (n_steps = 0), which writes nothing.
+    auto control = [&](bool advance) -> Surfaces<G> {
+#pragma clang fp contract(off)
+        // the law's words never change within a launch; re-read every step, or the compiler keeps them in registers across the RK4
+        asm volatile("" ::: "memory");
+        const double Vc = ld.get(SD_REF + FD_SVR_SPEED), hc = ld.get(SD_REF + FD_SVR_ALTITUDE), pc = ld.get(SD_REF + FD_SVR_HEADING);
+        // 1. errors: differences in fp64 from the stored state, then the glue type
+        const S V = M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]);
+        err[FD_SVI_SPEED] = G(double(V) - Vc);
+        err[FD_SVI_ALTITUDE] = G(-double(x[FD_X_D]) - hc);
+        err[FD_SVI_HEADING] = wrap_angle<G>(G(double(x[FD_X_YAW]) - pc));
+        G e[FD_NSVI];
+#pragma unroll
+        for (int k = 0; k < FD_NSVI; ++k) { const G lim = G(limits[k]); e[k] = clipv<G>(err[k], -lim, lim); }
+        // 2. deviations
+        const G dV = G(Vc - ld.get(SD_V0));
+        G dl[NLON], da[NLAT];
+        dl[0] = G(double(x[FD_X_U]) - ld.get(SD_X0 + 0)) - dV * lg.get(SG_CU);
+        dl[1] = G(double(x[FD_X_W]) - ld.get(SD_X0 + 1)) - dV * lg.get(SG_CW);
+        dl[2] = G(double(x[FD_X_Q]) - ld.get(SD_X0 + 2));
+        dl[3] = wrap_angle<G>(G(double(x[FD_X_PITCH]) - ld.get(SD_X0 + 3)));
+        dl[4] = -e[FD_SVI_ALTITUDE];
+        dl[5] = lg.get(SG_INT + FD_SVI_SPEED);
+        dl[6] = lg.get(SG_INT + FD_SVI_ALTITUDE);
+        da[0] = G(double(x[FD_X_V]) - ld.get(SD_X0 + 4));
+        da[1] = G(double(x[FD_X_P]) - ld.get(SD_X0 + 5));
+        da[2] = G(double(x[FD_X_R]) - ld.get(SD_X0 + 6));
+        da[3] = wrap_angle<G>(G(double(x[FD_X_ROLL]) - ld.get(SD_X0 + 7)));
+        da[4] = e[FD_SVI_HEADING];
+        da[5] = lg.get(SG_INT + FD_SVI_HEADING);
+        // 3. u = u0 - K d, each row summed left to right
+        G s[4];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            G a = lg.get(SG_K + FD_SVK_LON + r * NLON) * dl[0];
+#pragma unroll
+            for (int c = 1; c < NLON; ++c) a = a + lg.get(SG_K + FD_SVK_LON + r * NLON + c) * dl[c];
+            s[r] = a;
+            G t = lg.get(SG_K + FD_SVK_LAT + r * NLAT) * da[0];
+#pragma unroll
+            for (int c = 1; c < NLAT; ++c) t = t + lg.get(SG_K + FD_SVK_LAT + r * NLAT + c) * da[c];
+            s[2 + r] = t;
+        }
+        Surfaces<G> u;
+        u.elevator = lg.get(SG_U0 + FD_U_ELEVATOR) - s[0]; u.throttle = lg.get(SG_U0 + FD_U_THROTTLE) - s[1];
+        u.aileron = lg.get(SG_U0 + FD_U_AILERON) - s[2]; u.rudder = lg.get(SG_U0 + FD_U_RUDDER) - s[3];
+        if (advance) {
+            const bool lon = outside(u.elevator, G(-1), G(1)) || outside(u.throttle, G(0), G(1));
+            const bool lat = outside(u.aileron, G(-1), G(1)) || outside(u.rudder, G(-1), G(1));
+            sat += (lon || lat) ? 1 : 0;
+            // 4. anti-windup: a block's integrators hold while one of its controls is clipped
+            const G gdt = G(dt);
+            if (!lon) {
+                lg.set(SG_INT + FD_SVI_SPEED, dl[5] + e[FD_SVI_SPEED] * gdt);
+                lg.set(SG_INT + FD_SVI_ALTITUDE, dl[6] + e[FD_SVI_ALTITUDE] * gdt);
+            }
+            if (!lat) lg.set(SG_INT + FD_SVI_HEADING, da[5] + e[FD_SVI_HEADING] * gdt);
+        }
+        return u;
+    };
+    // 6. the references move at their own rates, in fp64
+    auto move_refs = [&]() {
+#pragma clang fp contract(off)
+        const double ddt = double(dt);
+        ld.set(SD_REF + FD_SVR_ALTITUDE, ld.get(SD_REF + FD_SVR_ALTITUDE) + ld.get(SD_REF + FD_SVR_CLIMB_RATE) * ddt);
+        ld.set(SD_REF + FD_SVR_HEADING, wrap_angle<double>(ld.get(SD_REF + FD_SVR_HEADING) + ld.get(SD_REF + FD_SVR_TURN_RATE) * ddt));
+    };
+
+    if (n_steps == 0) {
+        surf = control(false);
+    } else if constexpr (FAST) {
+        FastRK f;
+        f.init(x);
+        const float hdt = float(S(0.5) * dt), fdt = float(dt), dt6 = float(dt / S(6));
+        for (int s = 0; s < n_steps; ++s) {
+            surf = control(true);
+            Controls<T> C;
+            C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
+            rk4_fast_step<S, false>(P, Lm, C, x, f, hdt, fdt, dt6);
+            move_refs();
+        }
+    } else {
+        for (int s = 0; s < n_steps; ++s) {
+            surf = control(true);
+            Controls<T> C;
+            C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
+            rk4_substeps<S, T>(P, Lm, C, x, dt, 1);
+            move_refs();
+        }
+    }
+    // the addresses of the stores below are recomputed from a lane index the compiler cannot equate with `i`, so that none of
+    // them lives across the step loop
+    int64_t ie = i;
+    asm volatile("" : "+v"(ie));
+    if (n_steps > 0) {
+#pragma unroll
+        for (int k = 0; k < FD_NX; ++k) xs[k * n + ie] = x[k];
+        if (sat_steps) sat_steps[ie] += sat;
+        ref[int64_t(FD_SVR_ALTITUDE) * n + ie] = ld.get(SD_REF + FD_SVR_ALTITUDE);
+        ref[int64_t(FD_SVR_HEADING) * n + ie] = ld.get(SD_REF + FD_SVR_HEADING);
+#pragma unroll
+        for (int k = 0; k < FD_NSVI; ++k) integ[int64_t(k) * n + ie] = double(lg.get(SG_INT + k));
+        if (err_out) {
+#pragma unroll
+            for (int k = 0; k < FD_NSVI; ++k) err_out[int64_t(k) * n + ie] = double(err[k]);
+        }
+    }
+    if (surf_out) {                                              // the controls as applied: after set_controls' clip
+        surf_out[FD_U_ELEVATOR * n + ie] = S(clipv<G>(surf.elevator, G(-1), G(1)));
+        surf_out[FD_U_AILERON * n + ie] = S(clipv<G>(surf.aileron, G(-1), G(1)));
+        surf_out[FD_U_RUDDER * n + ie] = S(clipv<G>(surf.rudder, G(-1), G(1)));
+        surf_out[FD_U_THROTTLE * n + ie] = S(clipv<G>(surf.throttle, G(0), G(1)));
+    }
+}
+
+template <typename S, typename T>
+int launch_step(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
+                const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps, S* surf_out,
+                int32_t* sat_steps, double* err_out, void* stream)
+{
+    static_assert(LB >= FD_MAX_TYPES * Params<double>::FD_ND_LANES, "stage_params needs that many threads");
+    if (n_steps < 0) return FDYN_ERR_BAD_SIZE;
+    FD_CHECK_FLEET(n, n_types, LB)
+    if (!x || !x0 || !u0 || !K || !ref || !integ || !limits || !params) return FDYN_ERR_NULL;
+    if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
+    return launch<LB>(servo_step_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                      surf_out, sat_steps, err_out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdyn_servo_design(const double* A, const double* B, const double* x0, const double* weights, int weights_per_lane, int64_t n,
+                      double* K, double* residual, int32_t* iters, int32_t* status, void* stream)
+{
+    FD_CHECK_FLEET(n, 1, TB)
+    if (!A || !B || !x0 || !weights || !K || !residual || !iters || !status) return FDYN_ERR_NULL;
+    return launch<TB>(servo_design_kernel, n, stream, A, B, x0, weights, weights_per_lane, n, K, residual, iters, status);
+}
+
+int fdyn_servo_step_f64(double* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
+                        const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps, double* surf_out,
+                        int32_t* sat_steps, double* err_out, void* stream)
+{ return launch_step<double, double>(x, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, stream); }
+
+int fdyn_servo_step_mixed(double* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
+                          const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps, double* surf_out,
+                          int32_t* sat_steps, double* err_out, void* stream)
+{ return launch_step<double, float>(x, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, stream); }
+
+int fdyn_servo_step_f32(float* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
+                        const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps, float* surf_out,
+                        int32_t* sat_steps, double* err_out, void* stream)
+{ return launch_step<float, float>(x, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, stream); }
+
+}  // extern "C"

@@ -20,6 +20,7 @@ from .params import AircraftParams, param_table
 class BatchedSixDOF:
     _trim = None                 # (TrimResult, scales) of the last .trim(): the point design_lqr designs at
     _lqr = _kalman = lqr_saturated_steps = None     # the last design_lqr() / design_kalman(); [N] int32 once an LQR / LQG step ran
+    _servo = servo = None        # the last design_servo() and the ServoState it started
 
     def __init__(self, n: int, precision: str = "f64", types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, device=None):
@@ -125,6 +126,48 @@ class BatchedSixDOF:
             dt = getattr(self, "dt", 0.01)
         Q.step_into(self.precision, self.x, design, self.params, self.type_index, dt, n_steps, self.u, self._saturated_steps())
         self.time += dt * n_steps
+
+    # LQ servo (hcrl_amd.servo): LQR with integral action, flown to heading, speed and altitude commands
+    def design_servo(self, weights=None, scales=None, strict: bool = True):
+        """An LQ-servo gain for every aircraft at the fleet's current trim (the last `.trim(...)`): ServoDesign with K [26][N],
+        status 0 = a certified stabilising gain.  weights: None (ServoWeights()), a ServoWeights, or penalties [17] / [17][N];
+        scales: None = the multipliers the trim was solved with.  strict: raise ValueError when an aircraft has no certified
+        gain.  Also starts the loop's state (`servo`: references at the trim's own airspeed, altitude and heading, moving at its
+        climb rate and turn rate; integrators zero).  The fleet's state is not touched."""
+        from . import servo as SV
+        res, trim_scales = self._need_trim("design_servo")
+        out = SV.design_servo(res, self.params, self.type_index, trim_scales if scales is None else scales, weights)
+        if strict:
+            SV.require_ok(out, f"{type(self).__name__}.design_servo")
+        self._servo = out
+        self.servo = SV.ServoState.at_trim(res.x0)
+        return out
+
+    def command_servo(self, heading=None, speed=None, altitude=None):
+        """New references for step_servo, each a scalar or N values (None: unchanged): heading (rad), speed (m/s), altitude (m).
+        A heading or an altitude command stops that reference's own motion (the trim's turn or climb)."""
+        self._need_servo("command_servo")
+        self.servo.command(heading, speed, altitude)
+
+    def step_servo(self, n_steps: int = 1, dt: Optional[float] = None):
+        """n_steps x {errors against the references -> u = u0 - K d, clipped as set_controls clips -> integrators (held per block
+        while one of its controls is clipped) -> one RK4 of dt -> the references move at their own rates} in ONE launch (dt None:
+        the fleet's own `dt` where it has one, else 0.01 s).  Needs design_servo() first.  `u` receives the last applied
+        controls, `lqr_saturated_steps` [N] int32 counts the steps in which a control was clipped, `servo.err` holds the last
+        errors.  The fleet integrates its airframes' own parameter blocks; where they differ from the designed ones the
+        integrators take up the difference."""
+        from . import servo as SV
+        design = self._need_servo("step_servo")
+        if dt is None:
+            dt = getattr(self, "dt", 0.01)
+        SV.step_into(self.precision, self.x, design, self.servo, self.params, self.type_index, dt, n_steps, self.u,
+                     self._saturated_steps(), self.servo.err)
+        self.time += dt * n_steps
+
+    def _need_servo(self, what: str):
+        if self._servo is None:
+            raise ValueError(f"{type(self).__name__}.{what}: the fleet has no servo design; call .design_servo() first")
+        return self._servo
 
     # LQG (hcrl_amd.lqg): the estimator beside the LQR, and the output-feedback loop on noisy measurements
     def design_kalman(self, dt: float, noise=None, scales=None, strict: bool = True):

@@ -1,0 +1,222 @@
+"""LQ servo for whole fleets: trim -> linearise -> DESIGN -> fly to heading, speed and altitude commands.
+
+`hcrl_amd.lqr` regulates every aircraft to the trim it was designed at and to nothing else.  The servo adds what a command needs:
+position (the down word) and heading enter the feedback, and the airspeed, altitude and heading errors are integrated, so a
+mismatch between the designed and the flown airframe leaves no standing error.  `fdyn_servo_design` (csrc/servo_kernels.hip) solves
+a 7-state longitudinal and a 6-state lateral Riccati equation per aircraft in fp64, one lane per aircraft; `fdyn_servo_step_*`
+flies the law (include/fdyn_servo.h) over the fleets' own integrator, n_steps per launch.
+
+    fleet = BatchedSixDOF(65536, "mixed", types=("rc_plane", "cessna"), type_index=idx)
+    fleet.trim(20.0)
+    fleet.design_servo()                          # ServoDesign: K [26][n], status 0 = a certified stabilising gain
+    fleet.command_servo(heading=np.radians(60), speed=24.0, altitude=130.0)
+    fleet.step_servo(n_steps=100, dt=0.01)
+
+Nothing here synchronises with the device except `describe_status` on a tensor element, `count_not_ok` and the `strict` check,
+which read results back on purpose.
+"""
+from dataclasses import dataclass, fields
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib, layout as L
+from . import trim as T
+
+STATUS_BITS = ((L.FD_SV_NOT_CONVERGED, "not converged"), (L.FD_SV_NO_CERTIFICATE, "no stability certificate"),
+               (L.FD_SV_BAD_INPUT, "invalid model, trim or weights"))
+# rows / columns of the two augmented blocks inside A [12][12] and B [12][4]: the states that are words of x; the integrators follow
+LONGITUDINAL_STATES = T.LONGITUDINAL_STATES + (L.FD_X_D,)
+LATERAL_STATES = T.LATERAL_STATES + (L.FD_X_YAW,)
+DEFAULT_LIMITS = (3.0, 10.0, 0.3)                 # error clips: m/s, m, rad
+
+
+@dataclass
+class ServoWeights(T.LaneTable):
+    """Bryson's rule: the largest acceptable excursion of each state of the two augmented blocks and of each control; the penalty
+    is 1 / max^2.  Scalars, or length-n arrays for a sweep of weight sets in one launch (`rows`)."""
+    u: object = 2.0            # m/s
+    w: object = 2.0            # m/s
+    q: object = 0.5            # rad/s
+    theta: object = 0.1        # rad
+    z: object = 2.0            # m
+    i_speed: object = 4.0      # m
+    i_altitude: object = 4.0   # m s
+    v: object = 2.0            # m/s
+    p: object = 1.0            # rad/s
+    r: object = 0.5            # rad/s
+    phi: object = 0.2          # rad
+    psi: object = 0.1          # rad
+    i_heading: object = 0.2    # rad s
+    elevator: object = 0.3     # normalised controls, as set_controls takes them
+    throttle: object = 0.3
+    aileron: object = 0.3
+    rudder: object = 0.3
+
+    ENTRY = "servo maximum"
+
+    def maxima(self):
+        """The seventeen maxima in FD_SVW_* order."""
+        return tuple(getattr(self, f.name) for f in fields(self))
+
+    _entries = maxima
+
+    @staticmethod
+    def _values(m: np.ndarray) -> np.ndarray:
+        """The penalties `vector` [FD_NSVW] and `rows` [FD_NSVW][n] return: 1 / max^2."""
+        with np.errstate(all="ignore"):
+            return 1.0 / (m * m)
+
+
+assert len(fields(ServoWeights)) == L.FD_NSVW
+
+
+def weights_tensor(weights, n: int, device) -> torch.Tensor:
+    """None (the defaults), a ServoWeights, or penalties as an array / tensor [FD_NSVW] or [FD_NSVW][n] -> float64 on the device."""
+    if weights is None:
+        weights = ServoWeights()
+    if isinstance(weights, ServoWeights):
+        return torch.as_tensor(weights.rows(n) if weights.per_lane else weights.vector(), device=device)
+    return T.table_tensor(weights, n, device, "weights", L.FD_NSVW)
+
+
+@dataclass
+class ServoDesign(T.StatusResult):
+    STATUS_BITS = STATUS_BITS
+    FAILURE = "have no certified stabilising servo gain"
+
+    K: torch.Tensor                         # [26][n] float64: K_lon 2 x 7 row-major, then K_lat 2 x 6 (FD_SVK_*)
+    residual: torch.Tensor                  # [n] float64: relative Riccati residual of the worse block (NaN: invalid input)
+    iterations: torch.Tensor                # [n] int32: doubling steps of the slower block
+    status: torch.Tensor                    # [n] int32: FD_SV_* bits, 0 = a certified stabilising gain
+    x0: Optional[torch.Tensor] = None       # [12][n] float64: the trim the model was cut at
+    u0: Optional[torch.Tensor] = None       # [4][n]  float64
+
+    def gains(self):
+        """(K_lon [2][7][n], K_lat [2][6][n]): views of K."""
+        return (self.K[L.FD_SVK_LON:L.FD_SVK_LAT].reshape(2, L.FD_SV_NLON, self.n),
+                self.K[L.FD_SVK_LAT:L.FD_NSVK].reshape(2, L.FD_SV_NLAT, self.n))
+
+    def closed_loop(self, A: torch.Tensor, B: torch.Tensor):
+        """(a_lon - b_lon K_lon [7][7][n], a_lat - b_lat K_lat [6][6][n]): the two augmented closed loops, with torch ops on the
+        device.  A [12][12][n], B [12][4][n]; needs the trim point the design carries."""
+        if self.x0 is None:
+            raise ValueError("the design carries no trim point (x0)")
+        (a_lon, b_lon), (a_lat, b_lat) = augmented_blocks(A, B, self.x0)
+        K_lon, K_lat = self.gains()
+        return (a_lon - torch.einsum("ikn,kjn->ijn", b_lon, K_lon), a_lat - torch.einsum("ikn,kjn->ijn", b_lat, K_lat))
+
+
+describe_status = ServoDesign.describe_status                # 'ok' or the names of the FD_SV_* bits set in one status word
+
+
+def augmented_blocks(A: torch.Tensor, B: torch.Tensor, x0: torch.Tensor):
+    """((a_lon [7][7][n], b_lon [7][2][n]), (a_lat [6][6][n], b_lat [6][2][n])): the models fdyn_servo_design solves, with torch ops."""
+    n = int(A.shape[-1])
+    z = lambda *s: torch.zeros((*s, n), dtype=A.dtype, device=A.device)   # noqa: E731
+    a_lon, b_lon, a_lat, b_lat = z(7, 7), z(7, 2), z(6, 6), z(6, 2)
+    lon, lat = list(LONGITUDINAL_STATES), list(LATERAL_STATES)
+    a_lon[:5, :5] = A[lon][:, lon]
+    b_lon[:5] = B[lon][:, list(T.LONGITUDINAL_CONTROLS)]
+    u0, w0 = x0[L.FD_X_U].to(A.dtype), x0[L.FD_X_W].to(A.dtype)
+    V0 = torch.sqrt(u0 * u0 + w0 * w0)
+    a_lon[5, 0], a_lon[5, 1], a_lon[6, 4] = u0 / V0, w0 / V0, -1.0
+    a_lat[:5, :5] = A[lat][:, lat]
+    b_lat[:5] = B[lat][:, list(T.LATERAL_CONTROLS)]
+    a_lat[5, 4] = 1.0
+    return (a_lon, b_lon), (a_lat, b_lat)
+
+
+def servo_into(A: torch.Tensor, B: torch.Tensor, x0: torch.Tensor, weights: torch.Tensor, out: Optional[ServoDesign] = None) -> ServoDesign:
+    """One launch of fdyn_servo_design on device tensors: A [12][12][n], B [12][4][n], x0 [12][n], weights [17] or [17][n], all
+    float64; with `out` given nothing is allocated (the form to capture in a graph)."""
+    n, dev = T.check_model(A, B, weights, "weights", L.FD_NSVW), A.device
+    if tuple(x0.shape) != (L.FD_NX, n) or x0.dtype != torch.float64:
+        raise ValueError(f"x0 must be [12][{n}] float64, got {tuple(x0.shape)} {x0.dtype}")
+    if out is None:
+        out = ServoDesign(torch.empty((L.FD_NSVK, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                          torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    rc = _lib.load().fdyn_servo_design(_lib.ptr(A), _lib.ptr(B), _lib.ptr(x0), _lib.ptr(weights), int(weights.dim() == 2), n,
+                                       _lib.ptr(out.K), _lib.ptr(out.residual), _lib.ptr(out.iterations), _lib.ptr(out.status),
+                                       _lib.current_stream())
+    _lib.check(rc, "fdyn_servo_design")
+    return out
+
+
+def design_servo(trim_result, params: torch.Tensor, type_index=None, scales=None, weights=None) -> ServoDesign:
+    """Linearise every aircraft at its trim (fdyn_linearize at x0, u0), then design.  params [n_types][FD_NP] on the device;
+    type_index [n] or None; scales as `trim.scale_rows` takes them; weights as `weights_tensor` takes them."""
+    A, B = T.linearize_at_trim(trim_result, params, type_index, scales)
+    out = servo_into(A, B, trim_result.x0, weights_tensor(weights, trim_result.n, A.device))
+    out.x0, out.u0 = trim_result.x0, trim_result.u0
+    return out
+
+
+def require_ok(design: ServoDesign, what: str = "design_servo"):
+    """ValueError naming how many lanes have no certified gain, and why for the first of them."""
+    design.require_ok(what)
+
+
+@dataclass
+class ServoState:
+    """What the loop carries between launches, all float64 on the device: the references, the integrators and the error clips."""
+    ref: torch.Tensor                       # [5][n]: V_c, h_c, psi_c, hdot_c, psidot_c (FD_SVR_*)
+    integ: torch.Tensor                     # [3][n]: i_V, i_h, i_psi (FD_SVI_*)
+    limits: torch.Tensor                    # [3]: error clips (m/s, m, rad)
+    err: torch.Tensor                       # [3][n]: the errors of the last control step flown, before their clip
+
+    @property
+    def n(self) -> int:
+        return int(self.ref.shape[1])
+
+    @classmethod
+    def at_trim(cls, x0: torch.Tensor, limits=DEFAULT_LIMITS) -> "ServoState":
+        """The state of a fleet that has just been trimmed at x0 [12][n]: references at the trim's own airspeed, altitude and
+        heading, moving at the trim's climb rate and turn rate; integrators zero.  Torch ops on x0's device, no read-back."""
+        x0 = x0.to(torch.float64)
+        n, dev = int(x0.shape[1]), x0.device
+        u, v, w = x0[L.FD_X_U], x0[L.FD_X_V], x0[L.FD_X_W]
+        phi, th = x0[L.FD_X_ROLL], x0[L.FD_X_PITCH]
+        q, r = x0[L.FD_X_Q], x0[L.FD_X_R]
+        sph, cph, sth, cth = torch.sin(phi), torch.cos(phi), torch.sin(th), torch.cos(th)
+        ref = torch.empty((L.FD_NSVR, n), dtype=torch.float64, device=dev)
+        ref[L.FD_SVR_SPEED] = torch.sqrt(u * u + v * v + w * w)
+        ref[L.FD_SVR_ALTITUDE] = -x0[L.FD_X_D]
+        ref[L.FD_SVR_HEADING] = x0[L.FD_X_YAW]
+        ref[L.FD_SVR_CLIMB_RATE] = u * sth - v * sph * cth - w * cph * cth                 # -d(down)/dt
+        ref[L.FD_SVR_TURN_RATE] = (q * sph + r * cph) / cth                                # d(psi)/dt
+        return cls(ref, torch.zeros((L.FD_NSVI, n), dtype=torch.float64, device=dev),
+                   torch.as_tensor(np.asarray(limits, np.float64).reshape(L.FD_NSVI), device=dev),
+                   torch.zeros((L.FD_NSVI, n), dtype=torch.float64, device=dev))
+
+    def command(self, heading=None, speed=None, altitude=None):
+        """New references, each a scalar or n values (None: unchanged).  A heading or altitude command stops that reference's own
+        motion: its rate word goes to zero."""
+        dev = self.ref.device
+        for row, v in ((L.FD_SVR_SPEED, speed), (L.FD_SVR_ALTITUDE, altitude), (L.FD_SVR_HEADING, heading),
+                       (L.FD_SVR_CLIMB_RATE, None if altitude is None else 0.0), (L.FD_SVR_TURN_RATE, None if heading is None else 0.0)):
+            if v is None:
+                continue
+            t = v.to(device=dev, dtype=torch.float64) if isinstance(v, torch.Tensor) else \
+                torch.as_tensor(T.broadcast_rows(self.n, (v,), "servo command")[0], device=dev)
+            if row == L.FD_SVR_HEADING:
+                t = torch.remainder(t + np.pi, 2.0 * np.pi) - np.pi
+            self.ref[row] = t
+
+
+def step_into(precision: str, x: torch.Tensor, design: ServoDesign, state: ServoState, params: torch.Tensor,
+              type_index: Optional[torch.Tensor], dt: float, n_steps: int, surf_out: Optional[torch.Tensor] = None,
+              sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None):
+    """One launch of fdyn_servo_step_<precision>: x [12][n] in the precision's storage type, advanced in place with the state's
+    references and integrators; n_steps = 0 writes surf_out alone."""
+    if design.x0 is None or design.u0 is None:
+        raise ValueError("the design carries no trim point (x0, u0)")
+    n = int(x.shape[1])
+    if x.dtype != _lib.state_dtype(precision) or design.n != n or state.n != n:
+        raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and the servo state of that fleet")
+    rc = getattr(_lib.load(), f"fdyn_servo_step_{precision}")(
+        _lib.ptr(x), _lib.ptr(design.x0), _lib.ptr(design.u0), _lib.ptr(design.K), _lib.ptr(state.ref), _lib.ptr(state.integ),
+        _lib.ptr(state.limits), _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps),
+        _lib.ptr(surf_out), _lib.ptr(sat_steps), _lib.ptr(err_out), _lib.current_stream())
+    _lib.check(rc, "fdyn_servo_step")

@@ -307,6 +307,28 @@ enum { FD_MO_ABSCISSA = 0, FD_MO_RADIUS, FD_MO_MIN_ABS, FD_MO_MIN_ZETA, FD_MO_N_
  * either way every eigenvalue and summary word of BOTH blocks of the lane is NaN                                          */
 enum { FD_MO_NOT_CONVERGED = 1, FD_MO_BAD_INPUT = 2 };
 
+/* ---- LQ servo (fdyn_servo_design / fdyn_servo_step_*, csrc/servo_kernels.hip, include/fdyn_servo.h) ------------------ */
+/* the two augmented blocks: longitudinal (u, w, q, theta, z, i_V, i_h | elevator, throttle), 7 states, z the down-position word
+ * and i_V, i_h the integrals of the airspeed and the altitude error; lateral (v, p, r, phi, psi, i_psi | aileron, rudder), 6 */
+enum { FD_SV_NLON = 7, FD_SV_NLAT = 6 };
+/* weights [FD_NSVW] fp64, all diagonal penalties: q of the seven longitudinal states, q of the six lateral states, r of
+ * (elevator, throttle), r of (aileron, rudder)                                                                            */
+enum { FD_SVW_Q_LON = 0, FD_SVW_Q_LAT = 7, FD_SVW_R_LON = 13, FD_SVW_R_LAT = 15, FD_NSVW = 17 };
+/* gains K [FD_NSVK][n] fp64: K_lon 2 x 7 row-major (rows elevator, throttle), then K_lat 2 x 6 (rows aileron, rudder)      */
+enum { FD_SVK_LON = 0, FD_SVK_LAT = 14, FD_NSVK = 26 };
+/* reference ref [FD_NSVR][n] fp64: commanded airspeed (m/s), altitude (m) and heading (rad), and the rates the altitude and
+ * heading commands move at by themselves (m/s, rad/s: the climb rate and the turn rate of the trim)                        */
+enum { FD_SVR_SPEED = 0, FD_SVR_ALTITUDE, FD_SVR_HEADING, FD_SVR_CLIMB_RATE, FD_SVR_TURN_RATE, FD_NSVR = 5 };
+/* integrators integ [FD_NSVI][n] fp64, error clips limits [FD_NSVI] fp64 and errors err_out [FD_NSVI][n]: airspeed, altitude,
+ * heading                                                                                                                 */
+enum { FD_SVI_SPEED = 0, FD_SVI_ALTITUDE, FD_SVI_HEADING, FD_NSVI = 3 };
+/* status bits of a servo design, with the meaning of FD_LQR_*; 0 = a CERTIFIED stabilising gain
+ *   NOT_CONVERGED   the doubling iteration hit its cap, a singular pivot or a non-finite value
+ *   NO_CERTIFICATE  X is not positive definite or the Riccati residual exceeds 1e-8
+ *   BAD_INPUT       a word of A, B or x0 that is read is not finite, a weight is not finite and > 0, or the trim's
+ *                   sqrt(u0^2 + w0^2) is not > 0: nothing was solved                                                       */
+enum { FD_SV_NOT_CONVERGED = 1, FD_SV_NO_CERTIFICATE = 2, FD_SV_BAD_INPUT = 4 };
+
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
 enum {
