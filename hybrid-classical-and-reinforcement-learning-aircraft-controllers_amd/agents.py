@@ -428,3 +428,56 @@ class LQServoAgent:
 
     def __repr__(self) -> str:
         return "LQServoAgent(level=HSA)"
+
+
+class LQServoWaypointAgent(LQServoAgent):
+    """The LQ servo under the waypoint guidance for one aircraft (fdyn_servo_mission_f64, include/fdyn_mission.h), with the
+    reference agents' surface: it enters at the WAYPOINT level and takes the `ControlCommand(mode=WAYPOINT, waypoint=)` that
+    WaypointAgent takes; the host MissionPlanner (hcrl_amd.mission) sequences the waypoints, as in the reference.  Built the way
+    LQServoAgent is: the kernel sees a one-waypoint table with acceptance radius 0, which it never completes; n_steps = 0 gives
+    the controls, then one step on a copy of the state that is thrown away advances the integrators and leaves the commands in
+    the references."""
+    MODE = ControlMode.WAYPOINT
+
+    def __init__(self, design, lane: int = 0, limits=None, guidance_type: str = "PP", flight_config=None):
+        self.guidance_type, self._flight_config = guidance_type, flight_config
+        super().__init__(design, lane, limits)
+
+    def get_control_level(self) -> ControlMode:
+        return ControlMode.WAYPOINT
+
+    @property
+    def mission(self):
+        """The one-waypoint ServoMission the kernel is handed: its statistics run over every call since reset()."""
+        return self._mission
+
+    def compute_action(self, command, state: AircraftState, dt: Optional[float] = None) -> ControlSurfaces:
+        """`command`: a ControlCommand in WAYPOINT mode (its waypoint's speed None keeps the current airspeed), or None to keep
+        flying to the last waypoint."""
+        from . import servo as SV
+        if command is not None:
+            if command.mode != ControlMode.WAYPOINT:
+                raise ValueError(f"LQServoWaypointAgent takes WAYPOINT commands, got {command.mode}")
+            self._mission.wps.copy_(torch.as_tensor(command_row(command).reshape(1, L.FD_NWP), device=self._fleet.device))
+            self._has_waypoint = True
+        if not self._has_waypoint:
+            raise ValueError("LQServoWaypointAgent has no waypoint yet: the first command must carry one")
+        f, dt = self._fleet, 0.01 if dt is None else dt
+        f.x.copy_(torch.as_tensor(state.to_vector(), device=f.device).reshape(L.FD_NX, 1))
+        SV.mission_into("f64", f.x, self._design, self._state, self._mission, f.params, None, dt, 0, f.u)
+        self._scratch.copy_(f.x)
+        SV.mission_into("f64", self._scratch, self._design, self._state, self._mission, f.params, None, dt, 1, None, None, self._state.err)
+        s = f.u[:, 0].cpu().numpy()
+        return ControlSurfaces(elevator=float(s[L.FD_U_ELEVATOR]), aileron=float(s[L.FD_U_AILERON]),
+                               rudder=float(s[L.FD_U_RUDDER]), throttle=float(s[L.FD_U_THROTTLE]))
+
+    def reset(self):
+        """References back to the trim's own; integrators to zero; the waypoint and the statistics forgotten."""
+        from . import servo as SV
+        super().reset()
+        self._mission = SV.ServoMission.start(np.zeros((1, L.FD_NWP)), 1, self._fleet.device, self.guidance_type, 0.0, "freeze",
+                                              self._flight_config)
+        self._has_waypoint = False
+
+    def __repr__(self) -> str:
+        return "LQServoWaypointAgent(level=WAYPOINT)"

@@ -8,6 +8,9 @@
 // fdyn_servo_step_*   n_steps x { errors against the references -> u = u0 - K d -> Controls::set (clips as set_controls does) ->
 //                     integrators, frozen per block while one of its controls is clipped -> one RK4 of dt -> the references move
 //                     at their own rates }, one launch, through the steppers of fdyn_core.hpp exactly as lqr_step_kernel calls them.
+// fdyn_servo_mission_* the same step with the PID cascade's mission update and waypoint guidance (fdyn_guidance.hpp) in front of it:
+//                     n_steps x { waypoint reached? -> heading, speed and altitude command -> the references -> the control step
+//                     above }, one launch (include/fdyn_mission.h).  One body, servo_step_body, behind a compile-time switch.
 //
 // Design: two 7 x 7 / 6 x 6 solves in fp64 do not fit the register file; the matrices the compiler cannot keep go to scratch.  The
 // kernel runs once per design, 64-lane workgroups.
@@ -17,8 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fdyn_fleet.hpp"
+#include "fdyn_guidance.hpp"
 #include "fdyn_riccati_n.hpp"
 #include "../../include/fdyn_servo.h"
+#include "../../include/fdyn_mission.h"
 
 using namespace fdyn;
 
@@ -160,25 +165,51 @@ enum { SG_K = 0, SG_U0 = FD_NSVK, SG_CU = SG_U0 + FD_NU, SG_CW, SG_INT, SG_N = S
 
 template <typename G> FD_DEV bool outside(G v, G lo, G hi) { return !(v >= lo && v <= hi); }     // true for NaN, as any_clipped
 
-template <typename S, typename T>
-__global__ void __launch_bounds__(LB, 1)
-servo_step_kernel(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,
-                  const double* __restrict__ K /*[26][n]*/, double* __restrict__ ref /*[5][n]*/, double* __restrict__ integ /*[3][n]*/,
-                  const double* __restrict__ limits /*[3]*/, const uint8_t* __restrict__ type, const double* __restrict__ params,
-                  int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out /*[4][n]*/, int32_t* __restrict__ sat_steps,
-                  double* __restrict__ err_out /*[3][n]*/)
+// What fdyn_servo_mission_* adds to a servo step (include/fdyn_mission.h); NoMission is the plain servo step.
+struct NoMission {};
+struct Mission {
+    int32_t* wp_idx; const double* consts /*[FD_NC]*/; const double* wps /*[n_wp][4]*/; int n_wp;
+    int32_t* reached_total; int32_t* steps_flown; double* stats /*[4][n]*/;
+};
+
+// The servo step, and with MISSION the mission update and the waypoint guidance in front of each control step: guidance writes its
+// three commands into the lane's SD_REF words, which the control step reads anyway, and the statistics into SD_STAT; of the
+// mission only the waypoint index and two counters live in registers across the RK4.
+template <typename S, typename T, bool MISSION, typename MA>
+FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,
+                            const double* __restrict__ K /*[26][n]*/, double* __restrict__ ref /*[5][n]*/, double* __restrict__ integ /*[3][n]*/,
+                            const double* __restrict__ limits /*[3]*/, const uint8_t* __restrict__ type, const double* __restrict__ params,
+                            int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out /*[4][n]*/, int32_t* __restrict__ sat_steps,
+                            double* __restrict__ err_out /*[3][n]*/, const MA& m)
 {
     using G = typename GlueOf<S, T>::type;
     constexpr bool FAST = sizeof(T) == 4;
+    constexpr int SD_STAT = SD_N, SD_WORDS = MISSION ? SD_N + FD_NMST : SD_N;
     __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
-    __shared__ double s_d[SD_N * LB];
+    __shared__ double s_d[SD_WORDS * LB];
     __shared__ G s_g[SG_N * LB];
+    __shared__ G s_consts[MISSION ? FD_NC_STAGED : 1];
+    __shared__ G s_wps[MISSION ? FD_MAX_WAYPOINTS * FD_NWP : 1];
     stage_params<FAST>(s_params, params, n_types);
+    if constexpr (MISSION) {
+        stage_guidance_consts<G>(s_consts, m.consts);
+        for (int k = threadIdx.x; k < m.n_wp * FD_NWP; k += blockDim.x) s_wps[k] = G(m.wps[k]);
+    }
     __syncthreads();
     const int64_t i = int64_t(blockIdx.x) * LB + threadIdx.x;
     if (i >= n) return;
     Column<double> ld(s_d);
     Column<G> lg(s_g);
+    int32_t idx = 0, reached = 0, flown = 0;                     // mission: the lane's waypoint, the waypoints reached and the steps flown here
+    bool restart = false;
+    if constexpr (MISSION) {
+        idx = m.wp_idx[i];
+        idx = idx < 0 ? 0 : idx;
+        restart = int(m.consts[FD_C_ON_COMPLETE]) == 1;
+        constexpr double START[FD_NMST] = { 0.0, 0.0, __builtin_inf(), 0.0 };
+#pragma unroll
+        for (int k = 0; k < FD_NMST; ++k) ld.set(SD_STAT + k, m.stats ? m.stats[int64_t(k) * n + i] : START[k]);
+    }
     {
 #pragma clang fp contract(off)
         constexpr int W[8] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL };
@@ -279,32 +310,97 @@ servo_step_kernel(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 
         ld.set(SD_REF + FD_SVR_HEADING, wrap_angle<double>(ld.get(SD_REF + FD_SVR_HEADING) + ld.get(SD_REF + FD_SVR_TURN_RATE) * ddt));
     };
 
-    if (n_steps == 0) {
+    // mission steps 1-4 (include/fdyn_mission.h) on the glue-type state `xg`: false when the mission is complete.  With `advance`
+    // false (n_steps = 0) only the commands are formed.  Everything it computes is dead when it returns.
+    auto guide = [&](const G (&xg)[FD_NX], auto&& derive, bool advance) -> bool {
+        if constexpr (MISSION) {
+            asm volatile("" ::: "memory");                       // the constants and the waypoints are re-read every step too
+            if (idx < m.n_wp && waypoint_reached<G>(s_consts, s_wps + idx * FD_NWP, xg)) { idx += 1; reached += 1; }   // mission.update
+            if (idx >= m.n_wp) { if (restart) idx = 0; else return false; }                                           // COMPLETE
+            const G* wp = s_wps + idx * FD_NWP;
+            const Derived<G> d = derive();
+            const GuidanceCmd<G> c = waypoint_guidance<G>(s_consts, wp, xg, d);
+            ld.set(SD_REF + FD_SVR_SPEED, double(c.speed));
+            ld.set(SD_REF + FD_SVR_ALTITUDE, double(c.altitude));
+            ld.set(SD_REF + FD_SVR_HEADING, double(c.heading));
+            ld.set(SD_REF + FD_SVR_CLIMB_RATE, 0.0);
+            ld.set(SD_REF + FD_SVR_TURN_RATE, 0.0);
+            if (advance) {
+#pragma clang fp contract(off)
+                auto raise = [&](int k, double v) { if (v > ld.get(SD_STAT + k)) ld.set(SD_STAT + k, v); };
+                raise(FD_MST_ALTITUDE_ERROR, double(M<G>::abs(d.altitude - wp[FD_WP_ALTITUDE])));
+                raise(FD_MST_ROLL, double(M<G>::abs(xg[FD_X_ROLL])));
+                if (double(d.airspeed) < ld.get(SD_STAT + FD_MST_MIN_AIRSPEED)) ld.set(SD_STAT + FD_MST_MIN_AIRSPEED, double(d.airspeed));
+                if (idx >= 1) {                                  // the leg wps[idx - 1] -> wps[idx], in the horizontal plane
+                    const G* from = wp - FD_NWP;
+                    const G ln = wp[FD_WP_NORTH] - from[FD_WP_NORTH], le = wp[FD_WP_EAST] - from[FD_WP_EAST];
+                    const G len = M<G>::sqrt(ln * ln + le * le);
+                    if (len >= G(1))
+                        raise(FD_MST_CROSS_TRACK, double(fdiv(M<G>::abs(ln * (xg[FD_X_E] - from[FD_WP_EAST]) - le * (xg[FD_X_N] - from[FD_WP_NORTH])), len)));
+                }
+                flown += 1;
+            }
+        }
+        return true;
+    };
+
+    // With a mission the controls-only call (n_steps = 0) is the first half of one pass through the step loop: guidance and the law have
+    // ONE call site per kernel, so the controls of an agent (n_steps = 0) equal those of a fleet lane (n_steps = 1) to the bit.
+    bool only = false, advance = true;
+    int iters = n_steps;
+    if constexpr (MISSION) { advance = n_steps > 0; iters = advance ? n_steps : 1; }
+    else only = n_steps == 0;
+    if (only) {
         surf = control(false);
     } else if constexpr (FAST) {
         FastRK f;
         f.init(x);
         const float hdt = float(S(0.5) * dt), fdt = float(dt), dt6 = float(dt / S(6));
-        for (int s = 0; s < n_steps; ++s) {
-            surf = control(true);
+        for (int s = 0; s < iters; ++s) {
+            if (!guide(f.x0, [&]() { return derived_fast(f); }, advance)) {
+                if (!advance) return;                            // controls only: a complete lane writes nothing at all
+                break;
+            }
+            surf = control(advance);
+            if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
             rk4_fast_step<S, false>(P, Lm, C, x, f, hdt, fdt, dt6);
-            move_refs();
+            if constexpr (!MISSION) move_refs();
         }
     } else {
-        for (int s = 0; s < n_steps; ++s) {
-            surf = control(true);
+        for (int s = 0; s < iters; ++s) {
+            if (!guide(x, [&]() { return derived<S>(x); }, advance)) {
+                if (!advance) return;
+                break;
+            }
+            surf = control(advance);
+            if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
             rk4_substeps<S, T>(P, Lm, C, x, dt, 1);
-            move_refs();
+            if constexpr (!MISSION) move_refs();
         }
     }
     // the addresses of the stores below are recomputed from a lane index the compiler cannot equate with `i`, so that none of
     // them lives across the step loop
     int64_t ie = i;
     asm volatile("" : "+v"(ie));
+    if constexpr (MISSION) {
+        if (n_steps > 0) {
+            m.wp_idx[ie] = idx;
+            if (m.reached_total) m.reached_total[ie] += reached;
+            if (flown == 0) return;                              // complete before its first step here: nothing else of the lane changes
+            if (m.steps_flown) m.steps_flown[ie] += flown;
+            ref[int64_t(FD_SVR_SPEED) * n + ie] = ld.get(SD_REF + FD_SVR_SPEED);
+            ref[int64_t(FD_SVR_CLIMB_RATE) * n + ie] = 0.0;
+            ref[int64_t(FD_SVR_TURN_RATE) * n + ie] = 0.0;
+            if (m.stats) {
+#pragma unroll
+                for (int k = 0; k < FD_NMST; ++k) m.stats[int64_t(k) * n + ie] = ld.get(SD_STAT + k);
+            }
+        }
+    }
     if (n_steps > 0) {
 #pragma unroll
         for (int k = 0; k < FD_NX; ++k) xs[k * n + ie] = x[k];
@@ -324,6 +420,39 @@ servo_step_kernel(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 
         surf_out[FD_U_RUDDER * n + ie] = S(clipv<G>(surf.rudder, G(-1), G(1)));
         surf_out[FD_U_THROTTLE * n + ie] = S(clipv<G>(surf.throttle, G(0), G(1)));
     }
+}
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_step_kernel(S* __restrict__ xs, const double* __restrict__ x0, const double* __restrict__ u0, const double* __restrict__ K,
+                  double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits, const uint8_t* __restrict__ type,
+                  const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out,
+                  int32_t* __restrict__ sat_steps, double* __restrict__ err_out)
+{
+    servo_step_body<S, T, false>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, NoMission{});
+}
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_mission_kernel(S* __restrict__ xs, const double* __restrict__ x0, const double* __restrict__ u0, const double* __restrict__ K,
+                     double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits, const uint8_t* __restrict__ type,
+                     const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out,
+                     int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Mission m)
+{
+    servo_step_body<S, T, true>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, m);
+}
+
+template <typename S, typename T>
+int launch_mission(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
+                   const Mission& m, const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps,
+                   S* surf_out, int32_t* sat_steps, double* err_out, void* stream)
+{
+    if (n_steps < 0 || m.n_wp < 1 || m.n_wp > FD_MAX_WAYPOINTS) return FDYN_ERR_BAD_SIZE;
+    FD_CHECK_FLEET(n, n_types, LB)
+    if (!x || !x0 || !u0 || !K || !ref || !integ || !limits || !params || !m.wp_idx || !m.consts || !m.wps) return FDYN_ERR_NULL;
+    if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
+    return launch<LB>(servo_mission_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                      surf_out, sat_steps, err_out, m);
 }
 
 template <typename S, typename T>
@@ -366,5 +495,20 @@ int fdyn_servo_step_f32(float* x, const double* x0, const double* u0, const doub
                         const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps, float* surf_out,
                         int32_t* sat_steps, double* err_out, void* stream)
 { return launch_step<float, float>(x, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, stream); }
+
+#define FD_SERVO_MISSION(NAME, S, T)                                                                                                   \
+    int fdyn_servo_mission_##NAME(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ,              \
+                                  const double* limits, int32_t* wp_idx, const double* consts, const double* wps, int n_wp,           \
+                                  const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps,          \
+                                  S* surf_out, int32_t* sat_steps, double* err_out, int32_t* reached_total, int32_t* steps_flown,     \
+                                  double* stats, void* stream)                                                                        \
+    {                                                                                                                                  \
+        return launch_mission<S, T>(x, x0, u0, K, ref, integ, limits, Mission{ wp_idx, consts, wps, n_wp, reached_total, steps_flown, stats }, \
+                                    type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, stream);                     \
+    }
+FD_SERVO_MISSION(f64, double, double)
+FD_SERVO_MISSION(mixed, double, float)
+FD_SERVO_MISSION(f32, float, float)
+#undef FD_SERVO_MISSION
 
 }  // extern "C"

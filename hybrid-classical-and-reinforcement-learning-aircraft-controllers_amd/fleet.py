@@ -21,6 +21,7 @@ class BatchedSixDOF:
     _trim = None                 # (TrimResult, scales) of the last .trim(): the point design_lqr designs at
     _lqr = _kalman = lqr_saturated_steps = None     # the last design_lqr() / design_kalman(); [N] int32 once an LQR / LQG step ran
     _servo = servo = None        # the last design_servo() and the ServoState it started
+    servo_mission = None         # the last start_servo_mission()
 
     def __init__(self, n: int, precision: str = "f64", types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, device=None):
@@ -163,6 +164,37 @@ class BatchedSixDOF:
         SV.step_into(self.precision, self.x, design, self.servo, self.params, self.type_index, dt, n_steps, self.u,
                      self._saturated_steps(), self.servo.err)
         self.time += dt * n_steps
+
+    # waypoint missions on the servo (include/fdyn_mission.h): the cascade's mission update and guidance in front of the servo law
+    def start_servo_mission(self, waypoints, guidance_type: str = "PP", acceptance_radius: Optional[float] = None,
+                            on_complete: str = "freeze", flight_config=None):
+        """A waypoint mission for fly_servo_mission, the same one for every aircraft: ServoMission (also kept as `servo_mission`)
+        with every aircraft at the first waypoint.  The arguments as BatchedCascade takes them.  Needs design_servo() first."""
+        from . import servo as SV
+        self._need_servo("start_servo_mission")
+        self.servo_mission = SV.ServoMission.start(waypoints, self.n, self.device, guidance_type, acceptance_radius, on_complete, flight_config)
+        return self.servo_mission
+
+    def fly_servo_mission(self, n_steps: int = 1, dt: Optional[float] = None):
+        """n_steps x {mission update -> guidance -> references -> the control step of step_servo} in ONE launch.  An aircraft whose
+        mission is complete stops where it is.  `u`, `lqr_saturated_steps` and `servo.err` as step_servo leaves them; `time`
+        advances by n_steps x dt (an aircraft's own flown time: servo_mission.mission_time(dt))."""
+        from . import servo as SV
+        design = self._need_servo("fly_servo_mission")
+        if self.servo_mission is None:
+            raise ValueError(f"{type(self).__name__}.fly_servo_mission: the fleet has no mission; call .start_servo_mission() first")
+        if dt is None:
+            dt = getattr(self, "dt", 0.01)
+        SV.mission_into(self.precision, self.x, design, self.servo, self.servo_mission, self.params, self.type_index, dt, n_steps, self.u,
+                        self._saturated_steps(), self.servo.err)
+        self.time += dt * n_steps
+
+    def servo_mission_complete(self) -> torch.Tensor:
+        """[N] bool on the device: the aircraft that have completed the mission."""
+        self._need_servo("servo_mission_complete")
+        if self.servo_mission is None:
+            raise ValueError(f"{type(self).__name__}.servo_mission_complete: the fleet has no mission; call .start_servo_mission() first")
+        return self.servo_mission.complete()
 
     def _need_servo(self, what: str):
         if self._servo is None:

@@ -12,6 +12,12 @@ flies the law (include/fdyn_servo.h) over the fleets' own integrator, n_steps pe
     fleet.command_servo(heading=np.radians(60), speed=24.0, altitude=130.0)
     fleet.step_servo(n_steps=100, dt=0.01)
 
+A waypoint mission puts the PID cascade's mission update and guidance in front of the same law, n steps per launch
+(`fdyn_servo_mission_*`, include/fdyn_mission.h; `ServoMission`, `mission_into`):
+
+    mission = fleet.start_servo_mission(square_mission(300.0, 100.0, 20.0), guidance_type="PP")
+    fleet.fly_servo_mission(n_steps=6000, dt=0.01)    # mission.complete(), mission.mission_time(0.01), mission.stats
+
 Nothing here synchronises with the device except `describe_status` on a tensor element, `count_not_ok` and the `strict` check,
 which read results back on purpose.
 """
@@ -220,3 +226,69 @@ def step_into(precision: str, x: torch.Tensor, design: ServoDesign, state: Servo
         _lib.ptr(state.limits), _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps),
         _lib.ptr(surf_out), _lib.ptr(sat_steps), _lib.ptr(err_out), _lib.current_stream())
     _lib.check(rc, "fdyn_servo_step")
+
+
+# ---- waypoint missions on the servo (include/fdyn_mission.h) ---------------------------------------------------------------------
+@dataclass
+class ServoMission:
+    """A waypoint mission a servo fleet flies, and what it carries between launches, on the device: one waypoint table and one set
+    of guidance constants for the whole fleet, then per aircraft the active waypoint, the waypoints reached, the steps flown
+    and the running statistics."""
+    wps: torch.Tensor                       # [n_wp][4] float64: north, east, altitude, speed (NaN = keep the current airspeed)
+    consts: torch.Tensor                    # [FD_NC] float64: config.cascade_consts; the guidance and mission words are read
+    wp_idx: torch.Tensor                    # [n] int32: the active waypoint; n_wp = the mission is complete
+    reached_total: torch.Tensor             # [n] int32
+    steps_flown: torch.Tensor               # [n] int32
+    stats: torch.Tensor                     # [FD_NMST][n] float64: FD_MST_* running extrema
+
+    @property
+    def n(self) -> int:
+        return int(self.wp_idx.shape[0])
+
+    @property
+    def n_wp(self) -> int:
+        return int(self.wps.shape[0])
+
+    @classmethod
+    def start(cls, waypoints, n: int, device, guidance_type: str = "PP", acceptance_radius: Optional[float] = None,
+              on_complete: str = "freeze", flight_config=None) -> "ServoMission":
+        """`waypoints`: a sequence of flight_types.Waypoint, or a table [n_wp][4] as config.waypoint_table writes it.  The other
+        arguments as BatchedCascade takes them."""
+        from .config import cascade_consts, waypoint_table
+        if isinstance(waypoints, torch.Tensor):
+            waypoints = waypoints.detach().cpu().numpy()
+        table = np.ascontiguousarray(waypoints, np.float64) if isinstance(waypoints, np.ndarray) else waypoint_table(waypoints)
+        if table.ndim != 2 or table.shape[1] != L.FD_NWP or not 1 <= table.shape[0] <= L.FD_MAX_WAYPOINTS:
+            raise ValueError(f"a mission is [1..{L.FD_MAX_WAYPOINTS}][{L.FD_NWP}] waypoint rows, got {table.shape}")
+        consts = cascade_consts(flight_config=flight_config, guidance_type=guidance_type, acceptance_radius=acceptance_radius,
+                                on_complete=on_complete)
+        stats = torch.zeros((L.FD_NMST, n), dtype=torch.float64, device=device)
+        stats[L.FD_MST_MIN_AIRSPEED] = float("inf")
+        zeros = lambda: torch.zeros(n, dtype=torch.int32, device=device)   # noqa: E731
+        return cls(torch.as_tensor(table, device=device), torch.as_tensor(consts, device=device), zeros(), zeros(), zeros(), stats)
+
+    def complete(self) -> torch.Tensor:
+        """[n] bool: the aircraft whose mission is complete (never true for a mission that restarts)."""
+        return self.wp_idx >= self.n_wp
+
+    def mission_time(self, dt: float) -> torch.Tensor:
+        """[n] float64: the time flown, steps_flown x dt."""
+        return self.steps_flown.to(torch.float64) * float(dt)
+
+
+def mission_into(precision: str, x: torch.Tensor, design: ServoDesign, state: ServoState, mission: ServoMission, params: torch.Tensor,
+                 type_index: Optional[torch.Tensor], dt: float, n_steps: int, surf_out: Optional[torch.Tensor] = None,
+                 sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None):
+    """One launch of fdyn_servo_mission_<precision>: n_steps x {mission update, guidance, servo law, RK4} on x [12][n], advanced in
+    place with the state's references and integrators and the mission's words; n_steps = 0 writes surf_out alone."""
+    if design.x0 is None or design.u0 is None:
+        raise ValueError("the design carries no trim point (x0, u0)")
+    n = int(x.shape[1])
+    if x.dtype != _lib.state_dtype(precision) or design.n != n or state.n != n or mission.n != n:
+        raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and the servo state and the mission of that fleet")
+    rc = getattr(_lib.load(), f"fdyn_servo_mission_{precision}")(
+        _lib.ptr(x), _lib.ptr(design.x0), _lib.ptr(design.u0), _lib.ptr(design.K), _lib.ptr(state.ref), _lib.ptr(state.integ),
+        _lib.ptr(state.limits), _lib.ptr(mission.wp_idx), _lib.ptr(mission.consts), _lib.ptr(mission.wps), mission.n_wp,
+        _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps), _lib.ptr(surf_out), _lib.ptr(sat_steps),
+        _lib.ptr(err_out), _lib.ptr(mission.reached_total), _lib.ptr(mission.steps_flown), _lib.ptr(mission.stats), _lib.current_stream())
+    _lib.check(rc, "fdyn_servo_mission")

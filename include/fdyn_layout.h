@@ -328,6 +328,11 @@ enum { FD_SVI_SPEED = 0, FD_SVI_ALTITUDE, FD_SVI_HEADING, FD_NSVI = 3 };
  *   BAD_INPUT       a word of A, B or x0 that is read is not finite, a weight is not finite and > 0, or the trim's
  *                   sqrt(u0^2 + w0^2) is not > 0: nothing was solved                                                       */
 enum { FD_SV_NOT_CONVERGED = 1, FD_SV_NO_CERTIFICATE = 2, FD_SV_BAD_INPUT = 4 };
+/* mission statistics stats [FD_NMST][n] fp64 of fdyn_servo_mission_* (include/fdyn_mission.h), running extrema carried across
+ * launches: the largest |altitude - the active waypoint's altitude| (m), the largest |roll| (rad), the smallest airspeed (m/s),
+ * the largest horizontal distance from the leg that ends at the active waypoint (m).  The host starts them at 0, 0, +inf, 0.
+ * (FD_MST_*, not FD_MS_*: that prefix and FD_NMS belong to the sensor's measurement block below.)                          */
+enum { FD_MST_ALTITUDE_ERROR = 0, FD_MST_ROLL, FD_MST_MIN_AIRSPEED, FD_MST_CROSS_TRACK, FD_NMST = 4 };
 
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
