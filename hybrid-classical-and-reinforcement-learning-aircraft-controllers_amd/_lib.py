@@ -54,6 +54,9 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo.h")) as _f
 # and the waypoint missions the servo flies (include/fdyn_mission.h): a fourth
 with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_mission.h")) as _f:
     MISSION_SIGNATURES = _parse_header(_f.read(), "include/fdyn_mission.h")[0]
+# and the servo and its missions in wind and gusts (include/fdyn_wind.h): a fifth
+with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_wind.h")) as _f:
+    WIND_SIGNATURES = _parse_header(_f.read(), "include/fdyn_wind.h")[0]
 
 _lib = None
 
@@ -77,7 +80,8 @@ def load():
         if torch.cuda.is_available():
             torch.cuda.init()
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *MODES_SIGNATURES.items(), *SERVO_SIGNATURES.items(), *MISSION_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *MODES_SIGNATURES.items(), *SERVO_SIGNATURES.items(), *MISSION_SIGNATURES.items(),
+                                  *WIND_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
         if lib.fdyn_abi_version() != FDYN_ABI_VERSION:

@@ -17,13 +17,19 @@
 // Step: the lane's law (26 gains, the trim point, references, integrators) does not fit beside the fp64 physics either: the words
 // live in LDS as [word][lane] columns of 64-lane workgroups, as lqg_step_kernel keeps its filter; a lane reads and writes its
 // own column only, so no barrier follows the staging one.
+// fdyn_servo_step_wind_*, fdyn_servo_mission_wind_*  the same body once more, in a moving air mass (include/fdyn_wind.h): steady
+//                     wind and a Gauss-Markov gust per aircraft.  Everything they add is behind the wind argument type; the still-
+//                     air kernels are built with NoWind.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fdyn_fleet.hpp"
 #include "fdyn_guidance.hpp"
 #include "fdyn_riccati_n.hpp"
+#include "fdyn_wind.hpp"
+#include "philox.hpp"
 #include "../../include/fdyn_servo.h"
 #include "../../include/fdyn_mission.h"
+#include "../../include/fdyn_wind.h"
 
 using namespace fdyn;
 
@@ -172,22 +178,43 @@ struct Mission {
     int32_t* reached_total; int32_t* steps_flown; double* stats /*[4][n]*/;
 };
 
+// What fdyn_*_wind_* add (include/fdyn_wind.h); NoWind is still air.
+struct NoWind {};
+struct AirMass { double* rows /*[FD_NSW][n]*/; uint64_t seed; const int32_t* step; const double* z /*[n_steps][3][n]*/; };
+// three standard normals from one Philox block, as the rate env's gust update forms and pairs them (fp32 Box-Muller: statistical use)
+FD_DEV void gust_normals(uint64_t seed, int64_t row, uint32_t step, double (&z)[3])
+{
+    uint32_t r[4];
+    philox4(seed, uint32_t(row), uint32_t(uint64_t(row) >> 32), step, FD_PHX_SERVO_GUST, r);
+    const float m0 = fast::sqrt(-2.0f * __logf(philox_u01(r[0]))), m1 = fast::sqrt(-2.0f * __logf(philox_u01(r[2])));
+    float s0, c0, s1, c1;
+    fast::sincos(6.283185307179586f * philox_u01(r[1]), s0, c0);
+    fast::sincos(6.283185307179586f * philox_u01(r[3]), s1, c1);
+    z[0] = double(m0 * c0); z[1] = double(m0 * s0); z[2] = double(m1 * c1);
+}
+
 // The servo step, and with MISSION the mission update and the waypoint guidance in front of each control step: guidance writes its
 // three commands into the lane's SD_REF words, which the control step reads anyway, and the statistics into SD_STAT; of the
 // mission only the waypoint index and two counters live in registers across the RK4.
-template <typename S, typename T, bool MISSION, typename MA>
+// With an AirMass (WINDY) the lane's W + g, as the stepper takes it, and its g, A, B and W live in further columns: the law and the
+// guidance read the air-relative velocity `air`, formed at the top of each control step and dead before the RK4.
+template <typename S, typename T, bool MISSION, typename MA, typename WA = NoWind>
 FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,
                             const double* __restrict__ K /*[26][n]*/, double* __restrict__ ref /*[5][n]*/, double* __restrict__ integ /*[3][n]*/,
                             const double* __restrict__ limits /*[3]*/, const uint8_t* __restrict__ type, const double* __restrict__ params,
                             int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out /*[4][n]*/, int32_t* __restrict__ sat_steps,
-                            double* __restrict__ err_out /*[3][n]*/, const MA& m)
+                            double* __restrict__ err_out /*[3][n]*/, const MA& m, const WA& wa = WA{})
 {
     using G = typename GlueOf<S, T>::type;
     constexpr bool FAST = sizeof(T) == 4;
-    constexpr int SD_STAT = SD_N, SD_WORDS = MISSION ? SD_N + FD_NMST : SD_N;
+    constexpr bool WINDY = !__is_same(WA, NoWind);
+    static_assert(__is_same(G, T), "the air-mass words are kept in the glue columns in the type the stepper takes");
+    constexpr int SD_STAT = SD_N, SD_GUST = MISSION ? SD_N + FD_NMST : SD_N;      // WINDY: g [3], then A, B, then W [3]
+    constexpr int SD_WIND = SD_GUST + 5, SD_WORDS = WINDY ? SD_WIND + 3 : SD_GUST;
+    constexpr int SG_AIR = SG_N, SG_WORDS = WINDY ? SG_N + 3 : SG_N;             // WINDY: W + g [3]
     __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
     __shared__ double s_d[SD_WORDS * LB];
-    __shared__ G s_g[SG_N * LB];
+    __shared__ G s_g[SG_WORDS * LB];
     __shared__ G s_consts[MISSION ? FD_NC_STAGED : 1];
     __shared__ G s_wps[MISSION ? FD_MAX_WAYPOINTS * FD_NWP : 1];
     stage_params<FAST>(s_params, params, n_types);
@@ -229,6 +256,13 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         for (int k = 0; k < FD_NU; ++k) lg.set(SG_U0 + k, G(u0[int64_t(k) * n + i]));
 #pragma unroll
         for (int k = 0; k < FD_NSVI; ++k) lg.set(SG_INT + k, G(integ[int64_t(k) * n + i]));
+        if constexpr (WINDY) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) ld.set(SD_GUST + k, wa.rows[int64_t(FD_SW_GUST_N + k) * n + i]);
+            // the steady wind too, so that the step loop reads nothing of the air mass from memory but z
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ld.set(SD_WIND + k, wa.rows[int64_t(FD_SW_WIND_N + k) * n + i]);
+        }
     }
     S x[FD_NX];
 #pragma unroll
@@ -240,6 +274,57 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     Surfaces<G> surf{ G(0), G(0), G(0), G(0) };
     G err[FD_NSVI] = { G(0), G(0), G(0) };
     int sat = 0;
+    // WINDY: the air-relative body velocity of this control step and its length, in the storage type
+    S air[3] = { S(0), S(0), S(0) }, Vair = S(0);
+    G Vguide = G(0);                                             // |v_air| as the guidance reads it (mixed, f32: derived_fast's form)
+    float nbw[3] = { 0.0f, 0.0f, 0.0f };                         // mixed, f32: -R^T (W + g)
+    uint32_t step0 = 0u;
+    if constexpr (WINDY) step0 = wa.step ? uint32_t(*wa.step) : 0u;
+    // a. the air mass of this control step, W + g summed in fp64, into its columns
+    auto set_air_mass = [&]() {
+        if constexpr (WINDY) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) lg.set(SG_AIR + k, G(ld.get(SD_WIND + k) + ld.get(SD_GUST + k)));
+        }
+    };
+    // b. v_air = v - R^T (W + g) from the given sines and cosines
+    auto set_air = [&](auto sphi, auto cphi, auto sth, auto cth, auto spsi, auto cpsi) {
+        if constexpr (WINDY) {
+#pragma clang fp contract(off)
+            using A = decltype(sphi);
+            A ua, va, wv;
+            if constexpr (FAST) {                                // the rotation in fp32, the difference in the storage type
+                air_relative<A>(A(0), A(0), A(0), sphi, cphi, sth, cth, spsi, cpsi, lg.get(SG_AIR + 0), lg.get(SG_AIR + 1), lg.get(SG_AIR + 2), ua, va, wv);
+                air[0] = x[FD_X_U] + S(ua); air[1] = x[FD_X_V] + S(va); air[2] = x[FD_X_W] + S(wv);
+                nbw[0] = ua; nbw[1] = va; nbw[2] = wv;
+            } else {
+                air_relative<A>(x[FD_X_U], x[FD_X_V], x[FD_X_W], sphi, cphi, sth, cth, spsi, cpsi, lg.get(SG_AIR + 0), lg.get(SG_AIR + 1), lg.get(SG_AIR + 2), ua, va, wv);
+                air[0] = ua; air[1] = va; air[2] = wv;
+            }
+            Vair = M<S>::sqrt((air[0] * air[0] + air[1] * air[1]) + air[2] * air[2]);
+            if constexpr (!FAST) Vguide = G(Vair);
+        }
+    };
+    auto air_mass = [&]() -> Wind<T> {
+        if constexpr (WINDY) return Wind<T>{ lg.get(SG_AIR + 0), lg.get(SG_AIR + 1), lg.get(SG_AIR + 2) };
+        else return Wind<T>{};
+    };
+    // f. the gust update of control step s of this launch
+    auto gust = [&](int s) {
+        if constexpr (WINDY) {
+            double zn[3];
+            if (wa.z) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) zn[k] = wa.z[(int64_t(s) * 3 + k) * n + i];
+            } else {
+                gust_normals(wa.seed, i, step0 + uint32_t(s) + 1u, zn);
+            }
+            const double ga = ld.get(SD_GUST + 3), gb = ld.get(SD_GUST + 4);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ld.set(SD_GUST + k, gust_update(ld.get(SD_GUST + k), ga, gb, zn[k]));
+        }
+    };
 
     // one control step up to the integrators: returns the unclipped controls (Controls::set clips).  `advance` is false for the
     // controls-only call (n_steps = 0), which writes nothing.
@@ -249,7 +334,9 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         asm volatile("" ::: "memory");
         const double Vc = ld.get(SD_REF + FD_SVR_SPEED), hc = ld.get(SD_REF + FD_SVR_ALTITUDE), pc = ld.get(SD_REF + FD_SVR_HEADING);
         // 1. errors: differences in fp64 from the stored state, then the glue type
-        const S V = M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]);
+        S V, xu = x[FD_X_U], xv = x[FD_X_V], xw = x[FD_X_W];
+        if constexpr (WINDY) { V = Vair; xu = air[0]; xv = air[1]; xw = air[2]; }
+        else V = M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]);
         err[FD_SVI_SPEED] = G(double(V) - Vc);
         err[FD_SVI_ALTITUDE] = G(-double(x[FD_X_D]) - hc);
         err[FD_SVI_HEADING] = wrap_angle<G>(G(double(x[FD_X_YAW]) - pc));
@@ -259,14 +346,14 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         // 2. deviations
         const G dV = G(Vc - ld.get(SD_V0));
         G dl[NLON], da[NLAT];
-        dl[0] = G(double(x[FD_X_U]) - ld.get(SD_X0 + 0)) - dV * lg.get(SG_CU);
-        dl[1] = G(double(x[FD_X_W]) - ld.get(SD_X0 + 1)) - dV * lg.get(SG_CW);
+        dl[0] = G(double(xu) - ld.get(SD_X0 + 0)) - dV * lg.get(SG_CU);
+        dl[1] = G(double(xw) - ld.get(SD_X0 + 1)) - dV * lg.get(SG_CW);
         dl[2] = G(double(x[FD_X_Q]) - ld.get(SD_X0 + 2));
         dl[3] = wrap_angle<G>(G(double(x[FD_X_PITCH]) - ld.get(SD_X0 + 3)));
         dl[4] = -e[FD_SVI_ALTITUDE];
         dl[5] = lg.get(SG_INT + FD_SVI_SPEED);
         dl[6] = lg.get(SG_INT + FD_SVI_ALTITUDE);
-        da[0] = G(double(x[FD_X_V]) - ld.get(SD_X0 + 4));
+        da[0] = G(double(xv) - ld.get(SD_X0 + 4));
         da[1] = G(double(x[FD_X_P]) - ld.get(SD_X0 + 5));
         da[2] = G(double(x[FD_X_R]) - ld.get(SD_X0 + 6));
         da[3] = wrap_angle<G>(G(double(x[FD_X_ROLL]) - ld.get(SD_X0 + 7)));
@@ -318,7 +405,8 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             if (idx < m.n_wp && waypoint_reached<G>(s_consts, s_wps + idx * FD_NWP, xg)) { idx += 1; reached += 1; }   // mission.update
             if (idx >= m.n_wp) { if (restart) idx = 0; else return false; }                                           // COMPLETE
             const G* wp = s_wps + idx * FD_NWP;
-            const Derived<G> d = derive();
+            Derived<G> d = derive();
+            if constexpr (WINDY) d.airspeed = Vguide;            // d. course, ground speed, position and altitude stay ground quantities
             const GuidanceCmd<G> c = waypoint_guidance<G>(s_consts, wp, xg, d);
             ld.set(SD_REF + FD_SVR_SPEED, double(c.speed));
             ld.set(SD_REF + FD_SVR_ALTITUDE, double(c.altitude));
@@ -350,13 +438,41 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     int iters = n_steps;
     if constexpr (MISSION) { advance = n_steps > 0; iters = advance ? n_steps : 1; }
     else only = n_steps == 0;
+    // WINDY, f64: the sines and cosines of the stored angles, in the state type
+    auto set_air_stored = [&]() {
+        if constexpr (WINDY) {
+            S sphi, cphi, sth, cth, spsi, cpsi;
+            M<S>::sincos(x[FD_X_ROLL], sphi, cphi);
+            M<S>::sincos(x[FD_X_PITCH], sth, cth);
+            M<S>::sincos(x[FD_X_YAW], spsi, cpsi);
+            set_air(sphi, cphi, sth, cth, spsi, cpsi);
+        }
+    };
+    // WINDY, mixed and f32: the integrator's carried ones, as derived_fast reads them
+    auto set_air_carried = [&](FastRK& f) {
+        if constexpr (WINDY) {
+            f.ensure_trig();
+            set_air(f.t0.phi.x, f.t0.phi.y, f.t0.th.x, f.t0.th.y, f.t0.psi.x, f.t0.psi.y);
+            if constexpr (MISSION) {                             // the guidance's airspeed: derived_fast's expression on the fp32 copy
+                const float u = f.x0[3] + nbw[0], v = f.x0[4] + nbw[1], w = f.x0[5] + nbw[2];
+                Vguide = fast::sqrt(__builtin_fmaf(u, u, __builtin_fmaf(v, v, w * w)));
+            }
+        }
+    };
     if (only) {
+        if constexpr (WINDY) {
+            set_air_mass();
+            if constexpr (FAST) { FastRK f; f.init(x); set_air_carried(f); }
+            else set_air_stored();
+        }
         surf = control(false);
     } else if constexpr (FAST) {
         FastRK f;
         f.init(x);
         const float hdt = float(S(0.5) * dt), fdt = float(dt), dt6 = float(dt / S(6));
         for (int s = 0; s < iters; ++s) {
+            set_air_mass();
+            set_air_carried(f);
             if (!guide(f.x0, [&]() { return derived_fast(f); }, advance)) {
                 if (!advance) return;                            // controls only: a complete lane writes nothing at all
                 break;
@@ -365,11 +481,14 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
-            rk4_fast_step<S, false>(P, Lm, C, x, f, hdt, fdt, dt6);
+            if constexpr (WINDY) { rk4_fast_step<S, false, true>(P, Lm, C, x, f, hdt, fdt, dt6, air_mass()); gust(s); }
+            else rk4_fast_step<S, false>(P, Lm, C, x, f, hdt, fdt, dt6);
             if constexpr (!MISSION) move_refs();
         }
     } else {
         for (int s = 0; s < iters; ++s) {
+            set_air_mass();
+            set_air_stored();
             if (!guide(x, [&]() { return derived<S>(x); }, advance)) {
                 if (!advance) return;
                 break;
@@ -378,7 +497,8 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
-            rk4_substeps<S, T>(P, Lm, C, x, dt, 1);
+            if constexpr (WINDY) { rk4_substeps<S, T, true, true>(P, Lm, C, x, dt, 1, air_mass()); gust(s); }
+            else rk4_substeps<S, T>(P, Lm, C, x, dt, 1);
             if constexpr (!MISSION) move_refs();
         }
     }
@@ -413,6 +533,10 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
 #pragma unroll
             for (int k = 0; k < FD_NSVI; ++k) err_out[int64_t(k) * n + ie] = double(err[k]);
         }
+        if constexpr (WINDY) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) wa.rows[int64_t(FD_SW_GUST_N + k) * n + ie] = ld.get(SD_GUST + k);
+        }
     }
     if (surf_out) {                                              // the controls as applied: after set_controls' clip
         surf_out[FD_U_ELEVATOR * n + ie] = S(clipv<G>(surf.elevator, G(-1), G(1)));
@@ -443,30 +567,57 @@ servo_mission_kernel(S* __restrict__ xs, const double* __restrict__ x0, const do
 }
 
 template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_step_wind_kernel(S* __restrict__ xs, const double* __restrict__ x0, const double* __restrict__ u0, const double* __restrict__ K,
+                       double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits, const uint8_t* __restrict__ type,
+                       const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out,
+                       int32_t* __restrict__ sat_steps, double* __restrict__ err_out, AirMass w)
+{
+    servo_step_body<S, T, false>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, NoMission{}, w);
+}
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_mission_wind_kernel(S* __restrict__ xs, const double* __restrict__ x0, const double* __restrict__ u0, const double* __restrict__ K,
+                          double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits, const uint8_t* __restrict__ type,
+                          const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out,
+                          int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Mission m, AirMass w)
+{
+    servo_step_body<S, T, true>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, m, w);
+}
+
+// `w`: NULL for the still-air entries, the air mass for the _wind ones (its rows are required)
+template <typename S, typename T>
 int launch_mission(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
                    const Mission& m, const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps,
-                   S* surf_out, int32_t* sat_steps, double* err_out, void* stream)
+                   S* surf_out, int32_t* sat_steps, double* err_out, void* stream, const AirMass* w = nullptr)
 {
     if (n_steps < 0 || m.n_wp < 1 || m.n_wp > FD_MAX_WAYPOINTS) return FDYN_ERR_BAD_SIZE;
     FD_CHECK_FLEET(n, n_types, LB)
     if (!x || !x0 || !u0 || !K || !ref || !integ || !limits || !params || !m.wp_idx || !m.consts || !m.wps) return FDYN_ERR_NULL;
+    if (w && !w->rows) return FDYN_ERR_NULL;
     if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
-    return launch<LB>(servo_mission_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
-                      surf_out, sat_steps, err_out, m);
+    if (!w) return launch<LB>(servo_mission_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                              surf_out, sat_steps, err_out, m);
+    return launch<LB>(servo_mission_wind_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                      surf_out, sat_steps, err_out, m, *w);
 }
 
 template <typename S, typename T>
 int launch_step(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
                 const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps, S* surf_out,
-                int32_t* sat_steps, double* err_out, void* stream)
+                int32_t* sat_steps, double* err_out, void* stream, const AirMass* w = nullptr)
 {
     static_assert(LB >= FD_MAX_TYPES * Params<double>::FD_ND_LANES, "stage_params needs that many threads");
     if (n_steps < 0) return FDYN_ERR_BAD_SIZE;
     FD_CHECK_FLEET(n, n_types, LB)
     if (!x || !x0 || !u0 || !K || !ref || !integ || !limits || !params) return FDYN_ERR_NULL;
+    if (w && !w->rows) return FDYN_ERR_NULL;
     if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
-    return launch<LB>(servo_step_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
-                      surf_out, sat_steps, err_out);
+    if (!w) return launch<LB>(servo_step_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                              surf_out, sat_steps, err_out);
+    return launch<LB>(servo_step_wind_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                      surf_out, sat_steps, err_out, *w);
 }
 
 }  // namespace
@@ -510,5 +661,30 @@ FD_SERVO_MISSION(f64, double, double)
 FD_SERVO_MISSION(mixed, double, float)
 FD_SERVO_MISSION(f32, float, float)
 #undef FD_SERVO_MISSION
+
+#define FD_SERVO_WIND(NAME, S, T)                                                                                                      \
+    int fdyn_servo_step_wind_##NAME(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ,            \
+                                    const double* limits, const uint8_t* type, const double* params, int n_types, int64_t n, double dt, \
+                                    int n_steps, S* surf_out, int32_t* sat_steps, double* err_out, double* wind, uint64_t seed,        \
+                                    const int32_t* step, const double* z, void* stream)                                                \
+    {                                                                                                                                  \
+        const AirMass w{ wind, seed, step, z };                                                                                        \
+        return launch_step<S, T>(x, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, \
+                                 stream, &w);                                                                                          \
+    }                                                                                                                                  \
+    int fdyn_servo_mission_wind_##NAME(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ,         \
+                                       const double* limits, int32_t* wp_idx, const double* consts, const double* wps, int n_wp,      \
+                                       const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps,     \
+                                       S* surf_out, int32_t* sat_steps, double* err_out, int32_t* reached_total, int32_t* steps_flown, \
+                                       double* stats, double* wind, uint64_t seed, const int32_t* step, const double* z, void* stream) \
+    {                                                                                                                                  \
+        const AirMass w{ wind, seed, step, z };                                                                                        \
+        return launch_mission<S, T>(x, x0, u0, K, ref, integ, limits, Mission{ wp_idx, consts, wps, n_wp, reached_total, steps_flown, stats }, \
+                                    type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, stream, &w);                  \
+    }
+FD_SERVO_WIND(f64, double, double)
+FD_SERVO_WIND(mixed, double, float)
+FD_SERVO_WIND(f32, float, float)
+#undef FD_SERVO_WIND
 
 }  // extern "C"

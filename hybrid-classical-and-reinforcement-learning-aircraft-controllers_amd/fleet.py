@@ -150,17 +150,22 @@ class BatchedSixDOF:
         self._need_servo("command_servo")
         self.servo.command(heading, speed, altitude)
 
-    def step_servo(self, n_steps: int = 1, dt: Optional[float] = None):
+    def step_servo(self, n_steps: int = 1, dt: Optional[float] = None, wind=None):
         """n_steps x {errors against the references -> u = u0 - K d, clipped as set_controls clips -> integrators (held per block
         while one of its controls is clipped) -> one RK4 of dt -> the references move at their own rates} in ONE launch (dt None:
         the fleet's own `dt` where it has one, else 0.01 s).  Needs design_servo() first.  `u` receives the last applied
         controls, `lqr_saturated_steps` [N] int32 counts the steps in which a control was clipped, `servo.err` holds the last
         errors.  The fleet integrates its airframes' own parameter blocks; where they differ from the designed ones the
-        integrators take up the difference."""
+        integrators take up the difference.  wind: a servo.ServoWind, the air each aircraft flies in (None: still air)."""
         from . import servo as SV
         design = self._need_servo("step_servo")
         if dt is None:
             dt = getattr(self, "dt", 0.01)
+        if wind is not None:
+            SV.step_into(self.precision, self.x, design, self.servo, self.params, self.type_index, dt, n_steps, self.u,
+                         self._saturated_steps(), self.servo.err, wind=wind)
+            self.time += dt * n_steps
+            return
         SV.step_into(self.precision, self.x, design, self.servo, self.params, self.type_index, dt, n_steps, self.u,
                      self._saturated_steps(), self.servo.err)
         self.time += dt * n_steps
@@ -175,16 +180,22 @@ class BatchedSixDOF:
         self.servo_mission = SV.ServoMission.start(waypoints, self.n, self.device, guidance_type, acceptance_radius, on_complete, flight_config)
         return self.servo_mission
 
-    def fly_servo_mission(self, n_steps: int = 1, dt: Optional[float] = None):
+    def fly_servo_mission(self, n_steps: int = 1, dt: Optional[float] = None, wind=None):
         """n_steps x {mission update -> guidance -> references -> the control step of step_servo} in ONE launch.  An aircraft whose
         mission is complete stops where it is.  `u`, `lqr_saturated_steps` and `servo.err` as step_servo leaves them; `time`
-        advances by n_steps x dt (an aircraft's own flown time: servo_mission.mission_time(dt))."""
+        advances by n_steps x dt (an aircraft's own flown time: servo_mission.mission_time(dt)).  wind: as step_servo takes it; the
+        guidance then reads the air-relative speed, course and position stay ground quantities (no wind-correction angle)."""
         from . import servo as SV
         design = self._need_servo("fly_servo_mission")
         if self.servo_mission is None:
             raise ValueError(f"{type(self).__name__}.fly_servo_mission: the fleet has no mission; call .start_servo_mission() first")
         if dt is None:
             dt = getattr(self, "dt", 0.01)
+        if wind is not None:
+            SV.mission_into(self.precision, self.x, design, self.servo, self.servo_mission, self.params, self.type_index, dt, n_steps, self.u,
+                            self._saturated_steps(), self.servo.err, wind=wind)
+            self.time += dt * n_steps
+            return
         SV.mission_into(self.precision, self.x, design, self.servo, self.servo_mission, self.params, self.type_index, dt, n_steps, self.u,
                         self._saturated_steps(), self.servo.err)
         self.time += dt * n_steps

@@ -31,4 +31,6 @@ def _parse(path):
 
 
 globals().update(_parse(_HDR))
+# the wind rows of the servo (FD_SW_*, FD_NSW, FD_PHX_SERVO_GUST) live in the header that declares their entry points
+globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_wind.h")))
 __all__ = [k for k in globals() if k.startswith("FD_")]

@@ -18,6 +18,12 @@ A waypoint mission puts the PID cascade's mission update and guidance in front o
     mission = fleet.start_servo_mission(square_mission(300.0, 100.0, 20.0), guidance_type="PP")
     fleet.fly_servo_mission(n_steps=6000, dt=0.01)    # mission.complete(), mission.mission_time(0.01), mission.stats
 
+Both fly in a moving air mass when given a `ServoWind` (include/fdyn_wind.h: a steady wind and a Gauss-Markov gust per aircraft):
+
+    wind = ServoWind.steady(fleet.n, fleet.device, speed=6.0, direction=np.radians(90.0))
+    fleet.x.copy_(wind.ground_state(fleet.x))         # a still-air trim, put in trim relative to its air
+    fleet.fly_servo_mission(n_steps=6000, dt=0.01, wind=wind)
+
 Nothing here synchronises with the device except `describe_status` on a tensor element, `count_not_ok` and the `strict` check,
 which read results back on purpose.
 """
@@ -211,16 +217,103 @@ class ServoState:
             self.ref[row] = t
 
 
+# ---- the air mass (include/fdyn_wind.h) ---------------------------------------------------------------------------------------------
+@dataclass
+class ServoWind:
+    """The air a servo fleet flies in, per aircraft, on the device: the steady wind, the gust and the gust's step coefficients
+    (NED, the air moving TOWARD +north / +east / +down), the key of the in-kernel draws and the count of control steps drawn."""
+    rows: torch.Tensor                      # [FD_NSW][n] float64: FD_SW_WIND_*, FD_SW_GUST_* (advanced), FD_SW_GUST_A, FD_SW_GUST_B
+    seed: int = 0
+    step: Optional[torch.Tensor] = None     # [1] int32 on the device; advanced by the host layer after every launch
+
+    def __post_init__(self):
+        if self.rows.dim() != 2 or int(self.rows.shape[0]) != L.FD_NSW or self.rows.dtype != torch.float64:
+            raise ValueError(f"wind rows must be [{L.FD_NSW}][n] float64, got {tuple(self.rows.shape)} {self.rows.dtype}")
+        if self.step is None:
+            self.step = torch.zeros(1, dtype=torch.int32, device=self.rows.device)
+
+    @property
+    def n(self) -> int:
+        return int(self.rows.shape[1])
+
+    @classmethod
+    def steady(cls, n: int, device, speed, direction, vertical=0.0, seed: int = 0) -> "ServoWind":
+        """A steady wind and no gust: `speed` m/s toward the heading `direction` (rad from north), `vertical` m/s down; each a
+        scalar or n values."""
+        speed, direction, vertical = T.broadcast_rows(n, (speed, direction, vertical), "wind")
+        rows = np.zeros((L.FD_NSW, n))
+        rows[L.FD_SW_WIND_N], rows[L.FD_SW_WIND_E], rows[L.FD_SW_WIND_D] = speed * np.cos(direction), speed * np.sin(direction), vertical
+        rows[L.FD_SW_GUST_A] = 1.0
+        return cls(torch.as_tensor(rows, device=device), seed)
+
+    @classmethod
+    def from_disturbances(cls, disturbances, n: int, V0, dt: float, device, generator=None, seed: int = 0) -> "ServoWind":
+        """Wind and turbulence drawn on the host from the ranges of a `disturbances.Disturbances` (wind_speed, wind_direction,
+        wind_vertical, turbulence_intensity, gust_length), uniformly and per aircraft, with `generator` (a numpy Generator).
+        V0: the airspeed the fleet flies at, a scalar or n values.  The gust of an aircraft is first-order Gauss-Markov with
+        sigma = intensity x V0 and length L: A = exp(-dt V0 / L), B = sigma sqrt(1 - A^2), g0 ~ N(0, sigma^2)."""
+        rng = np.random.default_rng() if generator is None else generator
+        draw = lambda r: rng.uniform(r[0], r[1], n)                       # noqa: E731
+        V0 = T.broadcast_rows(n, (V0,), "V0")[0]
+        speed, direction, vertical = draw(disturbances.wind_speed), draw(disturbances.wind_direction), draw(disturbances.wind_vertical)
+        sigma, length = draw(disturbances.turbulence_intensity) * V0, draw(disturbances.gust_length)
+        A = np.exp(-float(dt) * V0 / length)
+        rows = np.zeros((L.FD_NSW, n))
+        rows[L.FD_SW_WIND_N], rows[L.FD_SW_WIND_E], rows[L.FD_SW_WIND_D] = speed * np.cos(direction), speed * np.sin(direction), vertical
+        rows[L.FD_SW_GUST_N:L.FD_SW_GUST_N + 3] = rng.standard_normal((3, n)) * sigma
+        rows[L.FD_SW_GUST_A], rows[L.FD_SW_GUST_B] = A, sigma * np.sqrt(1.0 - A * A)
+        return cls(torch.as_tensor(rows, device=device), seed)
+
+    def air_mass(self) -> torch.Tensor:
+        """[3][n] float64: W + g, the velocity of each aircraft's air (NED)."""
+        return self.rows[L.FD_SW_WIND_N:L.FD_SW_WIND_N + 3] + self.rows[L.FD_SW_GUST_N:L.FD_SW_GUST_N + 3]
+
+    def ground_state(self, x: torch.Tensor) -> torch.Tensor:
+        """x [12][n] with v += R^T (W + g): a fleet started from a still-air trim is then in trim relative to its air.  Torch ops
+        on x's device, in fp64; the result has x's dtype."""
+        y = x.to(torch.float64).clone()
+        wn, we, wd = self.air_mass().to(y.device)
+        sphi, cphi = torch.sin(y[L.FD_X_ROLL]), torch.cos(y[L.FD_X_ROLL])
+        sth, cth = torch.sin(y[L.FD_X_PITCH]), torch.cos(y[L.FD_X_PITCH])
+        spsi, cpsi = torch.sin(y[L.FD_X_YAW]), torch.cos(y[L.FD_X_YAW])
+        a, b = cpsi * wn + spsi * we, cpsi * we - spsi * wn
+        c = sth * a + cth * wd
+        y[L.FD_X_U] += cth * a - sth * wd
+        y[L.FD_X_V] += cphi * b + sphi * c
+        y[L.FD_X_W] += cphi * c - sphi * b
+        return y.to(x.dtype)
+
+    def _args(self, n: int, n_steps: int, z: Optional[torch.Tensor]):
+        """The trailing argument group of the six entries, checked."""
+        if self.n != n:
+            raise ValueError(f"the wind holds {self.n} aircraft, the fleet {n}")
+        if z is not None and (tuple(z.shape) != (n_steps, 3, n) or z.dtype != torch.float64):
+            raise ValueError(f"z must be [{n_steps}][3][{n}] float64, got {tuple(z.shape)} {z.dtype}")
+        return _lib.ptr(self.rows), int(self.seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(self.step), _lib.ptr(z)
+
+
 def step_into(precision: str, x: torch.Tensor, design: ServoDesign, state: ServoState, params: torch.Tensor,
               type_index: Optional[torch.Tensor], dt: float, n_steps: int, surf_out: Optional[torch.Tensor] = None,
-              sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None):
+              sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None, wind: Optional[ServoWind] = None,
+              z: Optional[torch.Tensor] = None):
     """One launch of fdyn_servo_step_<precision>: x [12][n] in the precision's storage type, advanced in place with the state's
-    references and integrators; n_steps = 0 writes surf_out alone."""
+    references and integrators; n_steps = 0 writes surf_out alone.  With a `wind`, one launch of fdyn_servo_step_wind_<precision>
+    (its gust rows advanced, then its step counter by n_steps); z [n_steps][3][n] float64 replaces the in-kernel normals."""
     if design.x0 is None or design.u0 is None:
         raise ValueError("the design carries no trim point (x0, u0)")
     n = int(x.shape[1])
     if x.dtype != _lib.state_dtype(precision) or design.n != n or state.n != n:
         raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and the servo state of that fleet")
+    if wind is not None:
+        rc = getattr(_lib.load(), f"fdyn_servo_step_wind_{precision}")(
+            _lib.ptr(x), _lib.ptr(design.x0), _lib.ptr(design.u0), _lib.ptr(design.K), _lib.ptr(state.ref), _lib.ptr(state.integ),
+            _lib.ptr(state.limits), _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps),
+            _lib.ptr(surf_out), _lib.ptr(sat_steps), _lib.ptr(err_out), *wind._args(n, int(n_steps), z), _lib.current_stream())
+        _lib.check(rc, "fdyn_servo_step_wind")
+        wind.step += int(n_steps)
+        return
+    if z is not None:
+        raise ValueError("z replaces the gust normals of a wind; there is none")
     rc = getattr(_lib.load(), f"fdyn_servo_step_{precision}")(
         _lib.ptr(x), _lib.ptr(design.x0), _lib.ptr(design.u0), _lib.ptr(design.K), _lib.ptr(state.ref), _lib.ptr(state.integ),
         _lib.ptr(state.limits), _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps),
@@ -278,14 +371,28 @@ class ServoMission:
 
 def mission_into(precision: str, x: torch.Tensor, design: ServoDesign, state: ServoState, mission: ServoMission, params: torch.Tensor,
                  type_index: Optional[torch.Tensor], dt: float, n_steps: int, surf_out: Optional[torch.Tensor] = None,
-                 sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None):
+                 sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None, wind: Optional[ServoWind] = None,
+                 z: Optional[torch.Tensor] = None):
     """One launch of fdyn_servo_mission_<precision>: n_steps x {mission update, guidance, servo law, RK4} on x [12][n], advanced in
-    place with the state's references and integrators and the mission's words; n_steps = 0 writes surf_out alone."""
+    place with the state's references and integrators and the mission's words; n_steps = 0 writes surf_out alone.  With a `wind`,
+    one launch of fdyn_servo_mission_wind_<precision>, as step_into."""
     if design.x0 is None or design.u0 is None:
         raise ValueError("the design carries no trim point (x0, u0)")
     n = int(x.shape[1])
     if x.dtype != _lib.state_dtype(precision) or design.n != n or state.n != n or mission.n != n:
         raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and the servo state and the mission of that fleet")
+    if wind is not None:
+        rc = getattr(_lib.load(), f"fdyn_servo_mission_wind_{precision}")(
+            _lib.ptr(x), _lib.ptr(design.x0), _lib.ptr(design.u0), _lib.ptr(design.K), _lib.ptr(state.ref), _lib.ptr(state.integ),
+            _lib.ptr(state.limits), _lib.ptr(mission.wp_idx), _lib.ptr(mission.consts), _lib.ptr(mission.wps), mission.n_wp,
+            _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps), _lib.ptr(surf_out), _lib.ptr(sat_steps),
+            _lib.ptr(err_out), _lib.ptr(mission.reached_total), _lib.ptr(mission.steps_flown), _lib.ptr(mission.stats),
+            *wind._args(n, int(n_steps), z), _lib.current_stream())
+        _lib.check(rc, "fdyn_servo_mission_wind")
+        wind.step += int(n_steps)
+        return
+    if z is not None:
+        raise ValueError("z replaces the gust normals of a wind; there is none")
     rc = getattr(_lib.load(), f"fdyn_servo_mission_{precision}")(
         _lib.ptr(x), _lib.ptr(design.x0), _lib.ptr(design.u0), _lib.ptr(design.K), _lib.ptr(state.ref), _lib.ptr(state.integ),
         _lib.ptr(state.limits), _lib.ptr(mission.wp_idx), _lib.ptr(mission.consts), _lib.ptr(mission.wps), mission.n_wp,
