@@ -57,6 +57,9 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_mission.h")) as 
 # and the servo and its missions in wind and gusts (include/fdyn_wind.h): a fifth
 with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_wind.h")) as _f:
     WIND_SIGNATURES = _parse_header(_f.read(), "include/fdyn_wind.h")[0]
+# and the servo on noisy sensors, its Kalman design and its flight on the estimate (include/fdyn_servo_lqg.h): a sixth
+with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_lqg.h")) as _f:
+    SERVO_LQG_SIGNATURES = _parse_header(_f.read(), "include/fdyn_servo_lqg.h")[0]
 
 _lib = None
 
@@ -81,7 +84,7 @@ def load():
             torch.cuda.init()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *MODES_SIGNATURES.items(), *SERVO_SIGNATURES.items(), *MISSION_SIGNATURES.items(),
-                                  *WIND_SIGNATURES.items()):
+                                  *WIND_SIGNATURES.items(), *SERVO_LQG_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
         if lib.fdyn_abi_version() != FDYN_ABI_VERSION:

@@ -20,16 +20,23 @@
 // fdyn_servo_step_wind_*, fdyn_servo_mission_wind_*  the same body once more, in a moving air mass (include/fdyn_wind.h): steady
 //                     wind and a Gauss-Markov gust per aircraft.  Everything they add is behind the wind argument type; the still-
 //                     air kernels are built with NoWind.
+// fdyn_servo_kf_design, fdyn_servo_lqg_step_*  the servo on noisy sensors (include/fdyn_servo_lqg.h): a steady-state Kalman filter
+//                     on the five physical states of each block (fdyn_kalman_n.hpp at N = 5), and the same body a third time with
+//                     the measurement, the filter and the accounting around the law, behind the estimator argument type.  The
+//                     estimate, du_prev and -- fp32 glue -- the filter's 120 words are further glue columns; with fp64 glue the
+//                     filter would not fit the 64 KB a workgroup may declare and is read from the caller's rows every step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fdyn_fleet.hpp"
 #include "fdyn_guidance.hpp"
 #include "fdyn_riccati_n.hpp"
+#include "fdyn_kalman_n.hpp"
 #include "fdyn_wind.hpp"
 #include "philox.hpp"
 #include "../../include/fdyn_servo.h"
 #include "../../include/fdyn_mission.h"
 #include "../../include/fdyn_wind.h"
+#include "../../include/fdyn_servo_lqg.h"
 
 using namespace fdyn;
 
@@ -156,6 +163,81 @@ servo_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __r
     status[i] = st;
 }
 
+// The servo's estimator (include/fdyn_servo_lqg.h): the steady-state Kalman filter of the five physical states of each block,
+// fdyn_kalman_n.hpp at N = 5 -- kf_design_kernel's design, one lane per aircraft.  Both blocks go through one rolled loop; what
+// the compiler cannot keep of the 5 x 5 matrices goes to scratch, as in servo_design_kernel.
+__global__ void __launch_bounds__(TB)
+servo_kf_design_kernel(const double* __restrict__ A /*[144][n]*/, const double* __restrict__ B /*[48][n]*/, double dt,
+                       const double* __restrict__ noise /*[20] or [20][n]*/, int noise_per_lane, int64_t n,
+                       double* __restrict__ F /*[120][n]*/, double* __restrict__ residual, int32_t* __restrict__ iters,
+                       int32_t* __restrict__ status)
+{
+#pragma clang fp contract(off)
+    constexpr int NB = FD_SK_NB;
+    const int64_t i = int64_t(blockIdx.x) * TB + threadIdx.x;
+    if (i >= n) return;
+    double nz[FD_NSKN];
+    bool bad = !(dt > 1e-6) || dt > 1.0;
+#pragma unroll
+    for (int k = 0; k < FD_NSKN; ++k) {
+        nz[k] = noise_per_lane ? noise[k * n + i] : noise[k];
+        bad = bad || !(::isfinite(nz[k]) && nz[k] > 0.0);
+    }
+    // both blocks' words are read and tested before anything is solved: BAD_INPUT (dt, noise, either block) solves nothing
+#pragma unroll 1
+    for (int blk = 0; blk < 2; ++blk) {
+        MN<NB> a;
+        double b[NB][2];
+        bad = !load_block<NB>(A, B, n, i, blk ? LAT_W : LON_W, blk ? FD_U_AILERON : FD_U_ELEVATOR, blk ? FD_U_RUDDER : FD_U_THROTTLE, a, b) || bad;
+        bad = bad || !(row_norm<NB>(a) * dt <= KFN_NORM_MAX);
+    }
+    double res = 0.0;
+    int it_max = 0, st = 0;
+    if (!bad) {
+#pragma unroll 1
+        for (int blk = 0; blk < 2; ++blk) {
+            MN<NB> a, Phi;
+            double b[NB][2], Gam[NB][2], sg[NB], rate[NB];
+            load_block<NB>(A, B, n, i, blk ? LAT_W : LON_W, blk ? FD_U_AILERON : FD_U_ELEVATOR, blk ? FD_U_RUDDER : FD_U_THROTTLE, a, b);
+#pragma unroll
+            for (int r = 0; r < NB; ++r) {
+                sg[r] = blk ? nz[FD_SKN_SIGMA + NB + r] : nz[FD_SKN_SIGMA + r];
+                rate[r] = blk ? nz[FD_SKN_RATE + NB + r] : nz[FD_SKN_RATE + r];
+            }
+            discretise<NB>(a, b, dt, Phi, Gam);
+            KalmanResult<NB> r;
+            kalman_solve<NB>(Phi, sg, rate, dt, r);
+            res = nan_max(res, r.residual);
+            it_max = r.iters > it_max ? r.iters : it_max;
+            if (r.failed || !r.converged) st |= FD_KF_NOT_CONVERGED;
+            if (!r.gain_ok || !r.positive || !(r.residual <= RIC_RES_MAX)) st |= FD_KF_NO_CERTIFICATE;
+
+            double* Fphi = F + int64_t(FD_SKF_PHI_LON + blk * (FD_SKF_PHI_LAT - FD_SKF_PHI_LON)) * n + i;
+            double* Fgam = F + int64_t(FD_SKF_GAMMA_LON + blk * (FD_SKF_GAMMA_LAT - FD_SKF_GAMMA_LON)) * n + i;
+            double* Fl = F + int64_t(FD_SKF_L_LON + blk * (FD_SKF_L_LAT - FD_SKF_L_LON)) * n + i;
+#pragma unroll
+            for (int rr = 0; rr < NB; ++rr) {
+#pragma unroll
+                for (int c = 0; c < NB; ++c) { Fphi[int64_t(rr * NB + c) * n] = Phi.v[rr][c]; Fl[int64_t(rr * NB + c) * n] = r.L.v[rr][c]; }
+                Fgam[int64_t(rr * 2) * n] = Gam[rr][0];
+                Fgam[int64_t(rr * 2 + 1) * n] = Gam[rr][1];
+            }
+        }
+    }
+    if (bad) { st = FD_KF_BAD_INPUT; res = __builtin_nan(""); it_max = 0; }
+    if (st) {                                                    // pass-through: Phi = I, Gamma = 0, L = I -> xhat = y
+#pragma unroll
+        for (int k = 0; k < FD_NSKF; ++k) {
+            const bool gam = k >= FD_SKF_GAMMA_LON && k < FD_SKF_L_LON;
+            const int at = (k < FD_SKF_GAMMA_LON ? k : k - FD_SKF_L_LON) % (NB * NB);
+            F[int64_t(k) * n + i] = (!gam && at % (NB + 1) == 0) ? 1.0 : 0.0;
+        }
+    }
+    residual[i] = res;
+    iters[i] = it_max;
+    status[i] = st;
+}
+
 // ---- the closed loop ------------------------------------------------------------------------------------------------------------
 // One lane's column of [word][lane] LDS words.
 template <typename W> struct Column {
@@ -193,25 +275,66 @@ FD_DEV void gust_normals(uint64_t seed, int64_t row, uint32_t step, double (&z)[
     z[0] = double(m0 * c0); z[1] = double(m0 * s0); z[2] = double(m1 * c1);
 }
 
+// What fdyn_servo_lqg_step_* add (include/fdyn_servo_lqg.h); NoEstimator is the servo on the true state.
+struct NoEstimator {};
+struct Estimator {
+    const double* F /*[120][n]*/; const double* sigma /*[10]*/; double* xhat /*[10][n]*/; double* du_prev /*[4][n]*/;
+    uint64_t seed; const int32_t* step; const double* z /*[n_steps][10][n]*/; int feedback;
+    double* err_est; double* err_meas; double* chatter; double* meas_out;
+};
+// the f64 step with the filter's 120 fp64 words in dynamic LDS (61 440 B behind the static columns) instead of read from F: the
+// slower of the two placements on MI355X (one workgroup per CU instead of three), kept as fdyn_servo_lqg_step_f64_lds so that the
+// comparison can be repeated (scripts/servo_lqg_throughput.py)
+struct EstimatorDynLds : Estimator {};
+constexpr int DYN_F_BYTES = FD_NSKF * 64 * int(sizeof(double));
+// the ten estimated words inside x, their angles, and where the trim's word sits among the fp64 columns (z0, psi0 behind SD_LQG)
+__device__ constexpr int EST_W[FD_NSKX] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_D, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL, FD_X_YAW };
+constexpr int EST_PSI = 9;
+constexpr bool est_angle(int j) { return j == 3 || j == 8 || j == EST_PSI; }
+// twelve standard normals for lane i at this step: three Philox blocks, Box-Muller paired as lqg_step_kernel pairs its eight
+FD_DEV void servo_lqg_normals(uint64_t seed, int64_t i, uint32_t step, float (&z)[12])
+{
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        uint32_t r[4];
+        philox4(seed, uint32_t(i), uint32_t(i >> 32), step, FD_PHX_SERVO_LQG + uint32_t(b), r);
+        const float u0 = philox_u01(r[0]), u1 = philox_u01(r[1]);
+        const float u2 = philox_u01(r[2]), u3 = philox_u01(r[3]);
+        const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
+        z[4 * b + 0] = ra * __cosf(6.283185307f * u1); z[4 * b + 1] = ra * __sinf(6.283185307f * u1);
+        z[4 * b + 2] = rb * __cosf(6.283185307f * u3); z[4 * b + 3] = rb * __sinf(6.283185307f * u3);
+    }
+}
+
 // The servo step, and with MISSION the mission update and the waypoint guidance in front of each control step: guidance writes its
 // three commands into the lane's SD_REF words, which the control step reads anyway, and the statistics into SD_STAT; of the
 // mission only the waypoint index and two counters live in registers across the RK4.
 // With an AirMass (WINDY) the lane's W + g, as the stepper takes it, and its g, A, B and W live in further columns: the law and the
 // guidance read the air-relative velocity `air`, formed at the top of each control step and dead before the RK4.
-template <typename S, typename T, bool MISSION, typename MA, typename WA = NoWind>
+// With an Estimator (LQG) each control step measures, filters and accounts around the law (`estimate`, `account`): the law is the one
+// below, and reads the state the lane holds in `x`, into which the estimate's or the measurement's ten words are put for the
+// duration of the call while the true ones wait in `keep`.
+template <typename S, typename T, bool MISSION, typename MA, typename WA = NoWind, typename EA = NoEstimator>
 FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,
                             const double* __restrict__ K /*[26][n]*/, double* __restrict__ ref /*[5][n]*/, double* __restrict__ integ /*[3][n]*/,
                             const double* __restrict__ limits /*[3]*/, const uint8_t* __restrict__ type, const double* __restrict__ params,
                             int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out /*[4][n]*/, int32_t* __restrict__ sat_steps,
-                            double* __restrict__ err_out /*[3][n]*/, const MA& m, const WA& wa = WA{})
+                            double* __restrict__ err_out /*[3][n]*/, const MA& m, const WA& wa = WA{}, const EA& ea = EA{})
 {
     using G = typename GlueOf<S, T>::type;
     constexpr bool FAST = sizeof(T) == 4;
     constexpr bool WINDY = !__is_same(WA, NoWind);
+    constexpr bool LQG = !__is_same(EA, NoEstimator);
+    constexpr bool F_DYN = __is_same(EA, EstimatorDynLds);                       // fp64 glue: the filter's words in dynamic LDS
+    constexpr bool F_LDS = LQG && sizeof(G) == 4;                                // the filter's words in LDS (fp32 glue) or read from F
+    static_assert(!F_DYN || sizeof(G) == 8, "the fp32 glue keeps the filter in its static columns");
     static_assert(__is_same(G, T), "the air-mass words are kept in the glue columns in the type the stepper takes");
     constexpr int SD_STAT = SD_N, SD_GUST = MISSION ? SD_N + FD_NMST : SD_N;      // WINDY: g [3], then A, B, then W [3]
-    constexpr int SD_WIND = SD_GUST + 5, SD_WORDS = WINDY ? SD_WIND + 3 : SD_GUST;
-    constexpr int SG_AIR = SG_N, SG_WORDS = WINDY ? SG_N + 3 : SG_N;             // WINDY: W + g [3]
+    constexpr int SD_WIND = SD_GUST + 5, SD_LQG = WINDY ? SD_WIND + 3 : SD_GUST; // LQG: the trim's z and psi
+    constexpr int SD_KEEP = SD_LQG + 2, SD_WORDS = LQG ? SD_KEEP + FD_NSKX : SD_LQG;     // and the true ten words while the law reads x_f
+    constexpr int SG_AIR = SG_N, SG_XHAT = WINDY ? SG_N + 3 : SG_N;              // WINDY: W + g [3]; LQG: xhat [10], du_prev [4], F [120]
+    constexpr int SG_DU = SG_XHAT + FD_NSKX, SG_F = SG_DU + FD_NU;
+    constexpr int SG_WORDS = LQG ? (F_LDS ? SG_F + FD_NSKF : SG_F) : SG_XHAT;
     __shared__ double s_params[FD_MAX_TYPES * FD_NP_STAGED];
     __shared__ double s_d[SD_WORDS * LB];
     __shared__ G s_g[SG_WORDS * LB];
@@ -262,6 +385,29 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             // the steady wind too, so that the step loop reads nothing of the air mass from memory but z
 #pragma unroll
             for (int k = 0; k < 3; ++k) ld.set(SD_WIND + k, wa.rows[int64_t(FD_SW_WIND_N + k) * n + i]);
+        }
+        if constexpr (LQG) {
+            ld.set(SD_LQG + 0, x0[FD_X_D * n + i]);
+            ld.set(SD_LQG + 1, x0[FD_X_YAW * n + i]);
+#pragma unroll
+            for (int j = 0; j < FD_NSKX; ++j) lg.set(SG_XHAT + j, G(ea.xhat[int64_t(j) * n + i]));
+#pragma unroll
+            for (int k = 0; k < FD_NU; ++k) lg.set(SG_DU + k, G(ea.du_prev[int64_t(k) * n + i]));
+            if constexpr (F_LDS) {                               // a few words at a time, before the physics' own registers are loaded
+#pragma unroll
+                for (int k = 0; k < FD_NSKF; ++k) {
+                    if (k % 16 == 0) asm volatile("" ::: "memory");
+                    lg.set(SG_F + k, G(ea.F[int64_t(k) * n + i]));
+                }
+            }
+            if constexpr (F_DYN) {
+                extern __shared__ double s_dyn_f[];              // [120][lane]; the static columns before it end on a 16-byte boundary
+#pragma unroll
+                for (int k = 0; k < FD_NSKF; ++k) {
+                    if (k % 16 == 0) asm volatile("" ::: "memory");
+                    s_dyn_f[k * LB + threadIdx.x] = ea.F[int64_t(k) * n + i];
+                }
+            }
         }
     }
     S x[FD_NX];
@@ -397,6 +543,141 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         ld.set(SD_REF + FD_SVR_HEADING, wrap_angle<double>(ld.get(SD_REF + FD_SVR_HEADING) + ld.get(SD_REF + FD_SVR_TURN_RATE) * ddt));
     };
 
+    // ---- LQG (include/fdyn_servo_lqg.h): everything below is empty without an Estimator
+    uint32_t lstep0 = 0u;
+    // the lane index of the estimator's global addresses, made opaque anew every step: computed from `i` they are loop invariants,
+    // hoisted out of the step loop into registers that live across the RK4
+    int64_t il = i, nl = n;                                      // and the row stride, or every row's offset is hoisted as well
+    if constexpr (LQG) lstep0 = ea.step ? uint32_t(*ea.step) : 0u;
+    // the fp64 column of the trim's word j of the ten: SD_X0 holds (u, w, q, theta | v, p, r, phi), SD_LQG z and psi
+    auto trim_word = [&](int j) -> double { return ld.get(j == 4 ? SD_LQG : (j == EST_PSI ? SD_LQG + 1 : (j < 4 ? SD_X0 + j : SD_X0 + j - 1))); };
+    auto fword = [&](int k) -> G {
+        if constexpr (F_LDS) return lg.get(SG_F + k);
+        else if constexpr (F_DYN) { extern __shared__ double s_dyn_f[]; return G(s_dyn_f[k * LB + threadIdx.x]); }
+        else if constexpr (LQG) return G(ea.F[int64_t(k) * nl + il]);
+        else return G(0);
+    };
+    // the accumulators are the caller's words in global memory, added to step by step: no instantiation has 24 fp64 registers
+    // to spare across the RK4
+    auto add_square = [&](double* __restrict__ words, int row, double t) {
+#pragma clang fp contract(off)
+        if (words) words[int64_t(row) * nl + il] = words[int64_t(row) * nl + il] + t * t;
+    };
+    // step 5 for the five words of block b: x_f = x0 + f, in fp64 with psi wrapped, into x; the true words wait in their columns
+    // (exact: the storage type widened to fp64)
+    auto put = [&](int b, const G (&f)[FD_SK_NB]) {
+        if constexpr (LQG) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int r = 0; r < FD_SK_NB; ++r) {
+                const int j = FD_SK_NB * b + r;
+                double xf = trim_word(j) + double(f[r]);
+                if (j == EST_PSI) xf = wrap_angle<double>(xf);
+                ld.set(SD_KEEP + j, double(x[EST_W[j]]));
+                x[EST_W[j]] = S(xf);
+            }
+        }
+    };
+    // steps 1-5 of control step s: measure, filter, account, block by block; then the law's input goes into x
+    auto estimate = [&](int s) {
+        if constexpr (LQG) {
+#pragma clang fp contract(off)
+            constexpr int NB = FD_SK_NB;
+            asm volatile("" : "+v"(il), "+s"(nl) :: "memory");   // the filter words are re-read every step, as the law's
+            float zn[12] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+            if (!ea.z) servo_lqg_normals(ea.seed, i, lstep0 + uint32_t(s) + 1u, zn);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int o = NB * b, phi = b ? FD_SKF_PHI_LAT : FD_SKF_PHI_LON, gam = b ? FD_SKF_GAMMA_LAT : FD_SKF_GAMMA_LON;
+                const int lgn = b ? FD_SKF_L_LAT : FD_SKF_L_LON;
+                G d[NB], y[NB], old[NB], pred[NB], e[NB], xh[NB];
+#pragma unroll
+                for (int r = 0; r < NB; ++r) {
+                    const G t = G(double(x[EST_W[o + r]]) - trim_word(o + r));
+                    d[r] = est_angle(o + r) ? wrap_angle<G>(t) : t;
+                    const G z = ea.z ? G(ea.z[(int64_t(s) * FD_NSKX + o + r) * nl + il]) : G(zn[o + r]);
+                    y[r] = d[r] + G(ea.sigma[o + r]) * z;
+                    old[r] = lg.get(SG_XHAT + o + r);
+                }
+                const G du0 = lg.get(SG_DU + (b ? FD_U_AILERON : FD_U_ELEVATOR)), du1 = lg.get(SG_DU + (b ? FD_U_RUDDER : FD_U_THROTTLE));
+#pragma unroll
+                for (int r = 0; r < NB; ++r) {
+                    if constexpr (!F_LDS) asm volatile("" ::: "memory");   // one row of F in flight at a time, not all 120 words
+                    G p = fword(phi + NB * r) * old[0];
+#pragma unroll
+                    for (int c = 1; c < NB; ++c) p = p + fword(phi + NB * r + c) * old[c];
+                    const G g = fword(gam + 2 * r) * du0 + fword(gam + 2 * r + 1) * du1;
+                    pred[r] = p + g;
+                    e[r] = y[r] - pred[r];
+                }
+                if (b) e[NB - 1] = wrap_angle<G>(e[NB - 1]);     // the heading innovation
+#pragma unroll
+                for (int r = 0; r < NB; ++r) {
+                    if constexpr (!F_LDS) asm volatile("" ::: "memory");
+                    G c = fword(lgn + NB * r) * e[0];
+#pragma unroll
+                    for (int k = 1; k < NB; ++k) c = c + fword(lgn + NB * r + k) * e[k];
+                    xh[r] = pred[r] + c;
+                }
+                if (b) xh[NB - 1] = wrap_angle<G>(xh[NB - 1]);
+#pragma unroll
+                for (int r = 0; r < NB; ++r) {
+                    G de = xh[r] - d[r];
+                    if (o + r == EST_PSI) de = wrap_angle<G>(de);
+                    add_square(ea.err_est, o + r, double(de));
+                    add_square(ea.err_meas, o + r, double(y[r] - d[r]));
+                    if (ea.meas_out) ea.meas_out[int64_t(o + r) * nl + il] = double(y[r]);
+                    lg.set(SG_XHAT + o + r, xh[r]);
+                }
+                // the law's input of this block; the other block's d is still formed from the true words, which are its own
+                if (ea.feedback == FD_LQG_MEASUREMENT) put(b, y);
+                else if (ea.feedback == FD_LQG_ESTIMATE) put(b, xh);
+            }
+        }
+    };
+    // n_steps = 0: the law's input from the stored estimate
+    auto estimate_stored = [&]() {
+        if constexpr (LQG) {
+            if (ea.feedback != FD_LQG_TRUTH) {
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    G xh[FD_SK_NB];
+#pragma unroll
+                    for (int r = 0; r < FD_SK_NB; ++r) xh[r] = lg.get(SG_XHAT + FD_SK_NB * b + r);
+                    put(b, xh);
+                }
+            }
+        }
+    };
+    // step 6, after the law: the true words back into x, the errors of the true state, chatter and du_prev
+    auto account = [&](const Surfaces<G>& u) {
+        if constexpr (LQG) {
+#pragma clang fp contract(off)
+            asm volatile("" : "+v"(il), "+s"(nl));
+            if (ea.feedback != FD_LQG_TRUTH) {
+#pragma unroll
+                for (int j = 0; j < FD_NSKX; ++j) x[EST_W[j]] = S(ld.get(SD_KEEP + j));
+            }
+            // the errors of the true state, the law's own step 1, on the words the RK4 is about to read.  Formed HERE, and for every
+            // feedback: with this placement the f64 physics rounds as it does in servo_step_kernel and feedback = truth is that
+            // kernel bit for bit; formed before the law it had nine more fused multiply-adds and was not (supposed, not proven:
+            // the uncontracted products u u, v v, w w are then common to this expression and the integrator's first stage)
+            const S V = M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]);
+            err[FD_SVI_SPEED] = G(double(V) - ld.get(SD_REF + FD_SVR_SPEED));
+            err[FD_SVI_ALTITUDE] = G(-double(x[FD_X_D]) - ld.get(SD_REF + FD_SVR_ALTITUDE));
+            err[FD_SVI_HEADING] = wrap_angle<G>(G(double(x[FD_X_YAW]) - ld.get(SD_REF + FD_SVR_HEADING)));
+            const G c[FD_NU] = { clipv<G>(u.elevator, G(-1), G(1)), clipv<G>(u.aileron, G(-1), G(1)), clipv<G>(u.rudder, G(-1), G(1)),
+                                 clipv<G>(u.throttle, G(0), G(1)) };
+            static_assert(FD_U_ELEVATOR == 0 && FD_U_AILERON == 1 && FD_U_RUDDER == 2 && FD_U_THROTTLE == 3, "control order");
+#pragma unroll
+            for (int k = 0; k < FD_NU; ++k) {
+                const G u0k = lg.get(SG_U0 + k);
+                add_square(ea.chatter, k, double(c[k] - (u0k + lg.get(SG_DU + k))));
+                lg.set(SG_DU + k, c[k] - u0k);
+            }
+        }
+    };
+
     // mission steps 1-4 (include/fdyn_mission.h) on the glue-type state `xg`: false when the mission is complete.  With `advance`
     // false (n_steps = 0) only the commands are formed.  Everything it computes is dead when it returns.
     auto guide = [&](const G (&xg)[FD_NX], auto&& derive, bool advance) -> bool {
@@ -465,6 +746,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             if constexpr (FAST) { FastRK f; f.init(x); set_air_carried(f); }
             else set_air_stored();
         }
+        if constexpr (LQG) estimate_stored();
         surf = control(false);
     } else if constexpr (FAST) {
         FastRK f;
@@ -477,7 +759,9 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
                 if (!advance) return;                            // controls only: a complete lane writes nothing at all
                 break;
             }
+            if constexpr (LQG) estimate(s);
             surf = control(advance);
+            if constexpr (LQG) account(surf);
             if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
@@ -493,7 +777,9 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
                 if (!advance) return;
                 break;
             }
+            if constexpr (LQG) estimate(s);
             surf = control(advance);
+            if constexpr (LQG) account(surf);
             if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
@@ -536,6 +822,12 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         if constexpr (WINDY) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) wa.rows[int64_t(FD_SW_GUST_N + k) * n + ie] = ld.get(SD_GUST + k);
+        }
+        if constexpr (LQG) {
+#pragma unroll
+            for (int j = 0; j < FD_NSKX; ++j) ea.xhat[int64_t(j) * n + ie] = double(lg.get(SG_XHAT + j));
+#pragma unroll
+            for (int k = 0; k < FD_NU; ++k) ea.du_prev[int64_t(k) * n + ie] = double(lg.get(SG_DU + k));
         }
     }
     if (surf_out) {                                              // the controls as applied: after set_controls' clip
@@ -584,6 +876,44 @@ servo_mission_wind_kernel(S* __restrict__ xs, const double* __restrict__ x0, con
                           int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Mission m, AirMass w)
 {
     servo_step_body<S, T, true>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, m, w);
+}
+
+template <typename S, typename T, typename EA = Estimator>
+__global__ void __launch_bounds__(LB, 1)
+servo_lqg_step_kernel(S* __restrict__ xs, const double* __restrict__ x0, const double* __restrict__ u0, const double* __restrict__ K,
+                      double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits, const uint8_t* __restrict__ type,
+                      const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out,
+                      int32_t* __restrict__ sat_steps, double* __restrict__ err_out, EA e)
+{
+    servo_step_body<S, T, false>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, NoMission{},
+                                 NoWind{}, e);
+}
+
+// dyn_lds: the f64 step with the filter in dynamic LDS (fdyn_servo_lqg_step_f64_lds)
+template <typename S, typename T, bool DYN = false>
+int launch_lqg_step(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
+                    const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps, S* surf_out,
+                    int32_t* sat_steps, double* err_out, const Estimator& e, void* stream)
+{
+    if (n_steps < 0) return FDYN_ERR_BAD_SIZE;
+    FD_CHECK_FLEET(n, n_types, LB)
+    if (!x || !x0 || !u0 || !K || !ref || !integ || !limits || !params || !e.F || !e.sigma || !e.xhat || !e.du_prev) return FDYN_ERR_NULL;
+    if (e.feedback != FD_LQG_ESTIMATE && e.feedback != FD_LQG_MEASUREMENT && e.feedback != FD_LQG_TRUTH) return FDYN_ERR_BAD_SIZE;
+    if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
+    if constexpr (DYN) {
+        EstimatorDynLds ed;
+        static_cast<Estimator&>(ed) = e;
+        auto kernel = servo_lqg_step_kernel<S, T, EstimatorDynLds>;
+        // static + dynamic LDS pass 64 KB: the kernel is told once that it may ask for them
+        static const hipError_t allowed = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DYN_F_BYTES);
+        (void)allowed;
+        hipLaunchKernelGGL(kernel, dim3(unsigned((n + LB - 1) / LB)), dim3(LB), DYN_F_BYTES, (hipStream_t)stream, x, x0, u0, K, ref, integ, limits,
+                           type, params, n_types, n, S(dt), n_steps, surf_out, sat_steps, err_out, ed);
+        return int(hipGetLastError());
+    } else {
+        return launch<LB>(servo_lqg_step_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                          surf_out, sat_steps, err_out, e);
+    }
 }
 
 // `w`: NULL for the still-air entries, the air mass for the _wind ones (its rows are required)
@@ -686,5 +1016,30 @@ FD_SERVO_WIND(f64, double, double)
 FD_SERVO_WIND(mixed, double, float)
 FD_SERVO_WIND(f32, float, float)
 #undef FD_SERVO_WIND
+
+int fdyn_servo_kf_design(const double* A, const double* B, double dt, const double* noise, int noise_per_lane, int64_t n, double* F,
+                         double* residual, int32_t* iters, int32_t* status, void* stream)
+{
+    FD_CHECK_FLEET(n, 1, TB)
+    if (!A || !B || !noise || !F || !residual || !iters || !status) return FDYN_ERR_NULL;
+    return launch<TB>(servo_kf_design_kernel, n, stream, A, B, dt, noise, noise_per_lane, n, F, residual, iters, status);
+}
+
+#define FD_SERVO_LQG(NAME, S, T, DYN)                                                                                                     \
+    int fdyn_servo_lqg_step_##NAME(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ,             \
+                                   const double* limits, const uint8_t* type, const double* params, int n_types, int64_t n, double dt, \
+                                   int n_steps, S* surf_out, int32_t* sat_steps, double* err_out, const double* F, const double* sigma, \
+                                   double* xhat, double* du_prev, uint64_t seed, const int32_t* step, const double* z, int feedback,   \
+                                   double* err_est, double* err_meas, double* chatter, double* meas_out, void* stream)                 \
+    {                                                                                                                                  \
+        const Estimator e{ F, sigma, xhat, du_prev, seed, step, z, feedback, err_est, err_meas, chatter, meas_out };                   \
+        return launch_lqg_step<S, T, DYN>(x, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps,     \
+                                     err_out, e, stream);                                                                              \
+    }
+FD_SERVO_LQG(f64, double, double, false)
+FD_SERVO_LQG(mixed, double, float, false)
+FD_SERVO_LQG(f32, float, float, false)
+FD_SERVO_LQG(f64_lds, double, double, true)
+#undef FD_SERVO_LQG
 
 }  // extern "C"

@@ -22,6 +22,7 @@ class BatchedSixDOF:
     _lqr = _kalman = lqr_saturated_steps = None     # the last design_lqr() / design_kalman(); [N] int32 once an LQR / LQG step ran
     _servo = servo = None        # the last design_servo() and the ServoState it started
     servo_mission = None         # the last start_servo_mission()
+    _servo_kalman = servo_lqg = None    # the last design_servo_kalman() and the ServoLqgState it started
 
     def __init__(self, n: int, precision: str = "f64", types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, device=None):
@@ -211,6 +212,38 @@ class BatchedSixDOF:
         if self._servo is None:
             raise ValueError(f"{type(self).__name__}.{what}: the fleet has no servo design; call .design_servo() first")
         return self._servo
+
+    # the servo on noisy sensors (hcrl_amd.servo_lqg): the Kalman filter of the servo's ten physical words, and the servo flown on it
+    def design_servo_kalman(self, dt: float, noise=None, scales=None, strict: bool = True):
+        """A steady-state Kalman filter on (u, w, q, theta, z | v, p, r, phi, psi) for every aircraft at the fleet's current trim,
+        discretised at `dt`: ServoKalmanDesign with F [120][N], status 0 = a certified stable filter.  noise: None (the sensor
+        layer's default noise and the servo's default process-noise rates), a ServoKalmanNoise, or [20] / [20][N]; scales as
+        design_servo.  strict: raise ValueError when an aircraft has no certified filter.  Also starts the estimator's state
+        (`servo_lqg`: estimate at the trim, step word 0)."""
+        from . import servo_lqg as SL
+        res, trim_scales = self._need_trim("design_servo_kalman")
+        out = SL.design_servo_kalman(res, self.params, self.type_index, trim_scales if scales is None else scales, dt, noise)
+        if strict:
+            SL.require_ok(out, f"{type(self).__name__}.design_servo_kalman")
+        self._servo_kalman = out
+        self.servo_lqg = SL.ServoLqgState.zeros(self.n, self.device, seed=getattr(self, "seed", 0) or 0)
+        return out
+
+    def step_servo_lqg(self, n_steps: int = 1, feedback: str = "estimate", z=None):
+        """n_steps x {measure the ten words with the sensor noise -> Kalman update, heading innovation wrapped -> the control step
+        of step_servo on trim + f -> one RK4 of the filter's dt -> the references move} in ONE launch, f = the estimate, the raw
+        measurement or the true state.  Needs design_servo() and design_servo_kalman() first.  z: None = in-kernel Philox draws
+        keyed by `servo_lqg.seed` and `servo_lqg.step`, or [n_steps][10][N] float64 standard normals.  `u`, `lqr_saturated_steps`
+        and `servo.err` (the errors of the TRUE state) as step_servo leaves them; `servo_lqg` carries the estimate and the
+        accumulators (err_est, err_meas, chatter)."""
+        from . import servo_lqg as SL
+        design = self._need_servo("step_servo_lqg")
+        if self._servo_kalman is None:
+            raise ValueError(f"{type(self).__name__}.step_servo_lqg: the fleet has no servo filter; call .design_servo_kalman() first")
+        kalman = self._servo_kalman
+        SL.lqg_step_into(self.precision, self.x, design, kalman, self.servo, self.servo_lqg, self.params, self.type_index, kalman.dt,
+                         n_steps, feedback, z, self.u, self._saturated_steps(), self.servo.err)
+        self.time += kalman.dt * n_steps
 
     # LQG (hcrl_amd.lqg): the estimator beside the LQR, and the output-feedback loop on noisy measurements
     def design_kalman(self, dt: float, noise=None, scales=None, strict: bool = True):

@@ -33,4 +33,6 @@ def _parse(path):
 globals().update(_parse(_HDR))
 # the wind rows of the servo (FD_SW_*, FD_NSW, FD_PHX_SERVO_GUST) live in the header that declares their entry points
 globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_wind.h")))
+# so do the words of the servo's estimator (FD_SKN_*, FD_SKF_*, FD_NSK*, FD_PHX_SERVO_LQG)
+globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_lqg.h")))
 __all__ = [k for k in globals() if k.startswith("FD_")]
