@@ -281,6 +281,17 @@ class BatchedSixDOF:
         from . import margins as M
         return M.loop_margins(*self._need_designs("loop_margins"), feedback, omega, curve)
 
+    def servo_loop_margins(self, feedback: str = "estimate", omega=None, curve: bool = False):
+        """LoopMargins of every aircraft's servo loop as `step_servo_lqg(feedback=...)` flies it in its linear region, at the filter's
+        dt: gain through a zero-order hold, integrators by forward Euler, and under "estimate" through the servo's filter.  Under
+        "truth" or "measurement" it is the loop of `step_servo` at that dt.  Needs design_servo() and design_servo_kalman() first.
+        omega: None = 64 points, logarithmic from 0.01 rad/s to the Nyquist rate.  The fleet's state is not touched."""
+        from . import servo_margins as SM
+        for design, lacks, call in ((self._servo, "stabilising servo gain", "design_servo()"), (self._servo_kalman, "stable servo filter", "design_servo_kalman(dt)")):
+            if design is None:
+                raise ValueError(f"{type(self).__name__}.servo_loop_margins: {self.n} of {self.n} aircraft have no certified {lacks} (call .{call} first)")
+        return SM.servo_loop_margins(self._servo, self._servo_kalman, self._servo.x0, feedback, omega, curve)
+
     # Flight modes (hcrl_amd.modes): where the poles are
     def modes(self, design=None, scales=None):
         """FleetModes of every aircraft linearised at the fleet's current trim (the last `.trim(...)`): the open-loop poles, or
