@@ -63,6 +63,9 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_lqg.h")) a
 # and the servo's loop margins (include/fdyn_servo_margins.h): a seventh
 with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_margins.h")) as _f:
     SERVO_MARGIN_SIGNATURES = _parse_header(_f.read(), "include/fdyn_servo_margins.h")[0]
+# and the servo's flight-mode report (include/fdyn_servo_modes.h): an eighth
+with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_modes.h")) as _f:
+    SERVO_MODES_SIGNATURES = _parse_header(_f.read(), "include/fdyn_servo_modes.h")[0]
 
 _lib = None
 
@@ -87,7 +90,8 @@ def load():
             torch.cuda.init()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *MODES_SIGNATURES.items(), *SERVO_SIGNATURES.items(), *MISSION_SIGNATURES.items(),
-                                  *WIND_SIGNATURES.items(), *SERVO_LQG_SIGNATURES.items(), *SERVO_MARGIN_SIGNATURES.items()):
+                                  *WIND_SIGNATURES.items(), *SERVO_LQG_SIGNATURES.items(), *SERVO_MARGIN_SIGNATURES.items(),
+                                  *SERVO_MODES_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
         if lib.fdyn_abi_version() != FDYN_ABI_VERSION:

@@ -292,6 +292,29 @@ class BatchedSixDOF:
                 raise ValueError(f"{type(self).__name__}.servo_loop_margins: {self.n} of {self.n} aircraft have no certified {lacks} (call .{call} first)")
         return SM.servo_loop_margins(self._servo, self._servo_kalman, self._servo.x0, feedback, omega, curve)
 
+    def servo_modes(self, loop: str = "continuous", scales=None):
+        """ServoModes of every aircraft's servo loop: "continuous" = the seven longitudinal and six lateral poles of the augmented
+        closed loop linearised at the fleet's current trim (scales: None = the multipliers the trim was solved with); "sampled" =
+        the same loops as `step_servo` flies them at the filter's dt, integrators by forward Euler; "filter" = the five + five
+        poles of the servo filter's error dynamics.  "continuous" needs design_servo(), "filter" design_servo_kalman(), "sampled"
+        both.  The fleet's state is not touched."""
+        from . import servo_modes as SMO
+        if loop not in SMO.LOOPS:
+            raise ValueError(f"loop must be one of {SMO.LOOPS}")
+        needs = {"continuous": (True, False), "sampled": (True, True), "filter": (False, True)}[loop]
+        for need, design, lacks, call in ((needs[0], self._servo, "stabilising servo gain", "design_servo()"),
+                                          (needs[1], self._servo_kalman, "stable servo filter", "design_servo_kalman(dt)")):
+            if need and design is None:
+                raise ValueError(f"{type(self).__name__}.servo_modes: {self.n} of {self.n} aircraft have no certified {lacks} (call .{call} first)")
+        if loop == "filter":
+            return self._servo_kalman.filter_poles()
+        if loop == "sampled":
+            return SMO.sampled_poles(self._servo, self._servo_kalman, self._servo.x0)
+        from . import trim as T
+        res, trim_scales = self._need_trim("servo_modes")
+        A, B = T.linearize_at_trim(res, self.params, self.type_index, trim_scales if scales is None else scales)
+        return self._servo.modes(A, B)
+
     # Flight modes (hcrl_amd.modes): where the poles are
     def modes(self, design=None, scales=None):
         """FleetModes of every aircraft linearised at the fleet's current trim (the last `.trim(...)`): the open-loop poles, or

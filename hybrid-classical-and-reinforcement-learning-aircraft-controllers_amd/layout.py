@@ -35,4 +35,6 @@ globals().update(_parse(_HDR))
 globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_wind.h")))
 # so do the words of the servo's estimator (FD_SKN_*, FD_SKF_*, FD_NSK*, FD_PHX_SERVO_LQG)
 globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_lqg.h")))
+# and the rows of the servo's flight-mode report (FD_SMO_*, FD_NSMO_*)
+globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_modes.h")))
 __all__ = [k for k in globals() if k.startswith("FD_")]

@@ -119,6 +119,14 @@ class ServoDesign(T.StatusResult):
         K_lon, K_lat = self.gains()
         return (a_lon - torch.einsum("ikn,kjn->ijn", b_lon, K_lon), a_lat - torch.einsum("ikn,kjn->ijn", b_lat, K_lat))
 
+    def modes(self, A: torch.Tensor, B: torch.Tensor):
+        """ServoModes of the two augmented closed loops (one launch of fdyn_servo_flight_modes): the seven longitudinal and six
+        lateral poles of the model A, B under these gains; needs the trim point the design carries."""
+        from . import servo_modes as SMO
+        if self.x0 is None:
+            raise ValueError("the design carries no trim point (x0)")
+        return SMO.flight_modes_into(A, B, self.x0, self.K)
+
 
 describe_status = ServoDesign.describe_status                # 'ok' or the names of the FD_SV_* bits set in one status word
 

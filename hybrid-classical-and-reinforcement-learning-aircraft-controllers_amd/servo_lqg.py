@@ -107,6 +107,12 @@ class ServoKalmanDesign(T.StatusResult):
         eye = torch.eye(NB, dtype=self.F.dtype, device=self.F.device)[None, :, :, None]
         return torch.einsum("bikn,bkjn->bijn", self.phi(), eye - self.gain())
 
+    def filter_poles(self):
+        """ServoModes of (I - L) Phi (one launch of fdyn_servo_filter_modes), five poles per block: spectral_radius() [2][n] < 1 is
+        the filter's stability.  Together with the sampled loop's poles they are the spectrum of the estimate-feedback loop."""
+        from . import servo_modes as SMO
+        return SMO.filter_modes_into(self.F)
+
 
 describe_status = ServoKalmanDesign.describe_status          # 'ok' or the names of the FD_KF_* bits set in one status word
 
