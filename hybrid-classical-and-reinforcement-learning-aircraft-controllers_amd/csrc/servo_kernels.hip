@@ -25,6 +25,10 @@
 //                     the measurement, the filter and the accounting around the law, behind the estimator argument type.  The
 //                     estimate, du_prev and -- fp32 glue -- the filter's 120 words are further glue columns; with fp64 glue the
 //                     filter would not fit the 64 KB a workgroup may declare and is read from the caller's rows every step.
+// fdyn_servo_lqg_mission_*  the mission flown on the estimate (include/fdyn_servo_lqg_mission.h): the body a fourth time, with
+//                     MISSION and an estimator both on.  The estimator runs FIRST here; a fixed-gain filter on a north / east
+//                     position measurement (the two spare normals of the estimator's draw) gives the guidance its position, and the
+//                     statistics stay on the true state.  Everything it adds is behind the EstimatorPos argument type.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fdyn_fleet.hpp"
@@ -37,6 +41,7 @@
 #include "../../include/fdyn_mission.h"
 #include "../../include/fdyn_wind.h"
 #include "../../include/fdyn_servo_lqg.h"
+#include "../../include/fdyn_servo_lqg_mission.h"
 
 using namespace fdyn;
 
@@ -286,6 +291,8 @@ struct Estimator {
 // slower of the two placements on MI355X (one workgroup per CU instead of three), kept as fdyn_servo_lqg_step_f64_lds so that the
 // comparison can be repeated (scripts/servo_lqg_throughput.py)
 struct EstimatorDynLds : Estimator {};
+// what fdyn_servo_lqg_mission_* add to the estimator (include/fdyn_servo_lqg_mission.h): the position filter of the guidance
+struct EstimatorPos : Estimator { const double* pos /*[2]*/; double* phat /*[2][n]*/; double* err_pos /*[2][n]*/; };
 constexpr int DYN_F_BYTES = FD_NSKF * 64 * int(sizeof(double));
 // the ten estimated words inside x, their angles, and where the trim's word sits among the fp64 columns (z0, psi0 behind SD_LQG)
 __device__ constexpr int EST_W[FD_NSKX] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_D, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL, FD_X_YAW };
@@ -314,6 +321,8 @@ FD_DEV void servo_lqg_normals(uint64_t seed, int64_t i, uint32_t step, float (&z
 // With an Estimator (LQG) each control step measures, filters and accounts around the law (`estimate`, `account`): the law is the one
 // below, and reads the state the lane holds in `x`, into which the estimate's or the measurement's ten words are put for the
 // duration of the call while the true ones wait in `keep`.
+// With MISSION and an EstimatorPos (LM) the order of a control step changes: estimate, position filter, then the guidance on `xg`
+// (the law's input with the filtered position), the law, `account`, and the statistics on the true state.
 template <typename S, typename T, bool MISSION, typename MA, typename WA = NoWind, typename EA = NoEstimator>
 FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,
                             const double* __restrict__ K /*[26][n]*/, double* __restrict__ ref /*[5][n]*/, double* __restrict__ integ /*[3][n]*/,
@@ -325,13 +334,17 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     constexpr bool FAST = sizeof(T) == 4;
     constexpr bool WINDY = !__is_same(WA, NoWind);
     constexpr bool LQG = !__is_same(EA, NoEstimator);
+    constexpr bool LM = __is_same(EA, EstimatorPos);                             // the mission on the estimate
+    static_assert(!LM || (MISSION && !WINDY), "the position filter belongs to the still-air mission");
+    constexpr int NZ = LM ? FD_NSKZ : FD_NSKX;                                   // normals per step of a replayed z
     constexpr bool F_DYN = __is_same(EA, EstimatorDynLds);                       // fp64 glue: the filter's words in dynamic LDS
     constexpr bool F_LDS = LQG && sizeof(G) == 4;                                // the filter's words in LDS (fp32 glue) or read from F
     static_assert(!F_DYN || sizeof(G) == 8, "the fp32 glue keeps the filter in its static columns");
     static_assert(__is_same(G, T), "the air-mass words are kept in the glue columns in the type the stepper takes");
     constexpr int SD_STAT = SD_N, SD_GUST = MISSION ? SD_N + FD_NMST : SD_N;      // WINDY: g [3], then A, B, then W [3]
     constexpr int SD_WIND = SD_GUST + 5, SD_LQG = WINDY ? SD_WIND + 3 : SD_GUST; // LQG: the trim's z and psi
-    constexpr int SD_KEEP = SD_LQG + 2, SD_WORDS = LQG ? SD_KEEP + FD_NSKX : SD_LQG;     // and the true ten words while the law reads x_f
+    constexpr int SD_KEEP = SD_LQG + 2, SD_PHAT = SD_KEEP + FD_NSKX;             // and the true ten words while the law reads x_f; LM: phat [2]
+    constexpr int SD_WORDS = LM ? SD_PHAT + 2 : (LQG ? SD_PHAT : SD_LQG);
     constexpr int SG_AIR = SG_N, SG_XHAT = WINDY ? SG_N + 3 : SG_N;              // WINDY: W + g [3]; LQG: xhat [10], du_prev [4], F [120]
     constexpr int SG_DU = SG_XHAT + FD_NSKX, SG_F = SG_DU + FD_NU;
     constexpr int SG_WORDS = LQG ? (F_LDS ? SG_F + FD_NSKF : SG_F) : SG_XHAT;
@@ -359,6 +372,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         constexpr double START[FD_NMST] = { 0.0, 0.0, __builtin_inf(), 0.0 };
 #pragma unroll
         for (int k = 0; k < FD_NMST; ++k) ld.set(SD_STAT + k, m.stats ? m.stats[int64_t(k) * n + i] : START[k]);
+        if constexpr (LM) { if (idx >= m.n_wp && !restart) return; }   // complete at entry: not even a measurement
     }
     {
 #pragma clang fp contract(off)
@@ -393,6 +407,10 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             for (int j = 0; j < FD_NSKX; ++j) lg.set(SG_XHAT + j, G(ea.xhat[int64_t(j) * n + i]));
 #pragma unroll
             for (int k = 0; k < FD_NU; ++k) lg.set(SG_DU + k, G(ea.du_prev[int64_t(k) * n + i]));
+            if constexpr (LM) {
+#pragma unroll
+                for (int k = 0; k < 2; ++k) ld.set(SD_PHAT + k, ea.phat[int64_t(k) * n + i]);
+            }
             if constexpr (F_LDS) {                               // a few words at a time, before the physics' own registers are loaded
 #pragma unroll
                 for (int k = 0; k < FD_NSKF; ++k) {
@@ -578,14 +596,20 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             }
         }
     };
+    float zpos[2] = { 0.0f, 0.0f };                              // LM: the two normals of the draw the estimator leaves over
+    G xg[LM ? FD_NX : 1];                                        // LM: the state the guidance reads
     // steps 1-5 of control step s: measure, filter, account, block by block; then the law's input goes into x
     auto estimate = [&](int s) {
         if constexpr (LQG) {
 #pragma clang fp contract(off)
             constexpr int NB = FD_SK_NB;
+            // LM: the step loop has a divergent exit, and a scalar carried round it through these statements would need a vector
+            // register at the join: start again from the arguments instead
+            if constexpr (LM) { il = i; nl = n; }
             asm volatile("" : "+v"(il), "+s"(nl) :: "memory");   // the filter words are re-read every step, as the law's
             float zn[12] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
             if (!ea.z) servo_lqg_normals(ea.seed, i, lstep0 + uint32_t(s) + 1u, zn);
+            if constexpr (LM) { zpos[0] = zn[FD_NSKX]; zpos[1] = zn[FD_NSKX + 1]; }
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 const int o = NB * b, phi = b ? FD_SKF_PHI_LAT : FD_SKF_PHI_LON, gam = b ? FD_SKF_GAMMA_LAT : FD_SKF_GAMMA_LON;
@@ -595,7 +619,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
                 for (int r = 0; r < NB; ++r) {
                     const G t = G(double(x[EST_W[o + r]]) - trim_word(o + r));
                     d[r] = est_angle(o + r) ? wrap_angle<G>(t) : t;
-                    const G z = ea.z ? G(ea.z[(int64_t(s) * FD_NSKX + o + r) * nl + il]) : G(zn[o + r]);
+                    const G z = ea.z ? G(ea.z[(int64_t(s) * NZ + o + r) * nl + il]) : G(zn[o + r]);
                     y[r] = d[r] + G(ea.sigma[o + r]) * z;
                     old[r] = lg.get(SG_XHAT + o + r);
                 }
@@ -635,6 +659,59 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             }
         }
     };
+    // LM, after estimate(): steps 1 (y_p), 4 and 5 of include/fdyn_servo_lqg_mission.h on the law's input in x, then the guidance's
+    // state: `seen` (what servo_mission_kernel's guidance reads) for truth, else x_f with the filtered or the measured position
+    auto position = [&](int s, bool adv, const G (&seen)[FD_NX]) {
+        if constexpr (LM) {
+#pragma clang fp contract(off)
+            const bool truth = ea.feedback == FD_LQG_TRUTH;
+            double yp[2] = { ld.get(SD_PHAT + 0), ld.get(SD_PHAT + 1) };
+            if (adv) {
+                G sphi, cphi, sth, cth, spsi, cpsi;
+                M<G>::sincos(G(x[FD_X_ROLL]), sphi, cphi);
+                M<G>::sincos(G(x[FD_X_PITCH]), sth, cth);
+                M<G>::sincos(G(x[FD_X_YAW]), spsi, cpsi);
+                const G u = G(x[FD_X_U]), v = G(x[FD_X_V]), w = G(x[FD_X_W]);
+                const G vne[2] = { (cth * cpsi) * u + ((sphi * sth) * cpsi - cphi * spsi) * v + ((cphi * sth) * cpsi + sphi * spsi) * w,
+                                   (cth * spsi) * u + ((sphi * sth) * spsi + cphi * cpsi) * v + ((cphi * sth) * spsi - sphi * cpsi) * w };
+                const double sp = ea.pos[FD_SPF_SIGMA], gain = ea.pos[FD_SPF_GAIN];
+                const double p[2] = { double(x[FD_X_N]), double(x[FD_X_E]) };    // never replaced by the law's input: the true position
+                double e2[2] = { 0.0, 0.0 };
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const double z = ea.z ? ea.z[(int64_t(s) * NZ + FD_NSKX + k) * nl + il] : double(zpos[k]);
+                    yp[k] = p[k] + sp * z;
+                    const double pm = ld.get(SD_PHAT + k) + double(dt) * double(vne[k]);
+                    const double ph = pm + gain * (yp[k] - pm);
+                    ld.set(SD_PHAT + k, ph);
+                    e2[0] = e2[0] + (ph - p[k]) * (ph - p[k]);
+                    e2[1] = e2[1] + (yp[k] - p[k]) * (yp[k] - p[k]);
+                }
+                if (ea.err_pos) {
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) ea.err_pos[int64_t(k) * nl + il] = ea.err_pos[int64_t(k) * nl + il] + e2[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < FD_NX; ++k) xg[k] = truth ? seen[k] : G(x[k]);
+            if (!truth) {
+                const bool est = ea.feedback == FD_LQG_ESTIMATE;
+                xg[FD_X_N] = G(est ? ld.get(SD_PHAT + 0) : yp[0]);
+                xg[FD_X_E] = G(est ? ld.get(SD_PHAT + 1) : yp[1]);
+            }
+        }
+    };
+    // the state the guidance reads: LM's own, else the caller's
+    auto seen_by_guidance = [&](const G (&own)[FD_NX]) -> const G (&)[FD_NX] { if constexpr (LM) return xg; else return own; };
+    // LM, a lane found complete: the true words back into x, as account() puts them back after the law
+    auto restore = [&]() {
+        if constexpr (LM) {
+            if (ea.feedback != FD_LQG_TRUTH) {
+#pragma unroll
+                for (int j = 0; j < FD_NSKX; ++j) x[EST_W[j]] = S(ld.get(SD_KEEP + j));
+            }
+        }
+    };
     // n_steps = 0: the law's input from the stored estimate
     auto estimate_stored = [&]() {
         if constexpr (LQG) {
@@ -653,6 +730,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     auto account = [&](const Surfaces<G>& u) {
         if constexpr (LQG) {
 #pragma clang fp contract(off)
+            if constexpr (LM) { il = i; nl = n; }
             asm volatile("" : "+v"(il), "+s"(nl));
             if (ea.feedback != FD_LQG_TRUTH) {
 #pragma unroll
@@ -678,6 +756,26 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         }
     };
 
+    // mission step 4 (include/fdyn_mission.h): the running extrema, on the state `xt` with its airspeed and altitude.  LM only, for
+    // the true state after the law; `guide` keeps its own copy of these lines in place, for the state it saw: calling this from
+    // there compiled the six mission kernels to other listings than the parent's
+    auto mission_stats = [&](const G (&xt)[FD_NX], G airspeed, G altitude) {
+        if constexpr (MISSION) {
+#pragma clang fp contract(off)
+            const G* wp = s_wps + idx * FD_NWP;
+            auto raise = [&](int k, double v) { if (v > ld.get(SD_STAT + k)) ld.set(SD_STAT + k, v); };
+            raise(FD_MST_ALTITUDE_ERROR, double(M<G>::abs(altitude - wp[FD_WP_ALTITUDE])));
+            raise(FD_MST_ROLL, double(M<G>::abs(xt[FD_X_ROLL])));
+            if (double(airspeed) < ld.get(SD_STAT + FD_MST_MIN_AIRSPEED)) ld.set(SD_STAT + FD_MST_MIN_AIRSPEED, double(airspeed));
+            if (idx >= 1) {                                      // the leg wps[idx - 1] -> wps[idx], in the horizontal plane
+                const G* from = wp - FD_NWP;
+                const G ln = wp[FD_WP_NORTH] - from[FD_WP_NORTH], le = wp[FD_WP_EAST] - from[FD_WP_EAST];
+                const G len = M<G>::sqrt(ln * ln + le * le);
+                if (len >= G(1))
+                    raise(FD_MST_CROSS_TRACK, double(fdiv(M<G>::abs(ln * (xt[FD_X_E] - from[FD_WP_EAST]) - le * (xt[FD_X_N] - from[FD_WP_NORTH])), len)));
+            }
+        }
+    };
     // mission steps 1-4 (include/fdyn_mission.h) on the glue-type state `xg`: false when the mission is complete.  With `advance`
     // false (n_steps = 0) only the commands are formed.  Everything it computes is dead when it returns.
     auto guide = [&](const G (&xg)[FD_NX], auto&& derive, bool advance) -> bool {
@@ -695,17 +793,21 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             ld.set(SD_REF + FD_SVR_CLIMB_RATE, 0.0);
             ld.set(SD_REF + FD_SVR_TURN_RATE, 0.0);
             if (advance) {
+                bool seen = true;                                // LM: the statistics are the TRUE state's, formed after the law
+                if constexpr (LM) seen = ea.feedback == FD_LQG_TRUTH;
+                if (seen) {
 #pragma clang fp contract(off)
-                auto raise = [&](int k, double v) { if (v > ld.get(SD_STAT + k)) ld.set(SD_STAT + k, v); };
-                raise(FD_MST_ALTITUDE_ERROR, double(M<G>::abs(d.altitude - wp[FD_WP_ALTITUDE])));
-                raise(FD_MST_ROLL, double(M<G>::abs(xg[FD_X_ROLL])));
-                if (double(d.airspeed) < ld.get(SD_STAT + FD_MST_MIN_AIRSPEED)) ld.set(SD_STAT + FD_MST_MIN_AIRSPEED, double(d.airspeed));
-                if (idx >= 1) {                                  // the leg wps[idx - 1] -> wps[idx], in the horizontal plane
-                    const G* from = wp - FD_NWP;
-                    const G ln = wp[FD_WP_NORTH] - from[FD_WP_NORTH], le = wp[FD_WP_EAST] - from[FD_WP_EAST];
-                    const G len = M<G>::sqrt(ln * ln + le * le);
-                    if (len >= G(1))
-                        raise(FD_MST_CROSS_TRACK, double(fdiv(M<G>::abs(ln * (xg[FD_X_E] - from[FD_WP_EAST]) - le * (xg[FD_X_N] - from[FD_WP_NORTH])), len)));
+                    auto raise = [&](int k, double v) { if (v > ld.get(SD_STAT + k)) ld.set(SD_STAT + k, v); };
+                    raise(FD_MST_ALTITUDE_ERROR, double(M<G>::abs(d.altitude - wp[FD_WP_ALTITUDE])));
+                    raise(FD_MST_ROLL, double(M<G>::abs(xg[FD_X_ROLL])));
+                    if (double(d.airspeed) < ld.get(SD_STAT + FD_MST_MIN_AIRSPEED)) ld.set(SD_STAT + FD_MST_MIN_AIRSPEED, double(d.airspeed));
+                    if (idx >= 1) {                              // the leg wps[idx - 1] -> wps[idx], in the horizontal plane
+                        const G* from = wp - FD_NWP;
+                        const G ln = wp[FD_WP_NORTH] - from[FD_WP_NORTH], le = wp[FD_WP_EAST] - from[FD_WP_EAST];
+                        const G len = M<G>::sqrt(ln * ln + le * le);
+                        if (len >= G(1))
+                            raise(FD_MST_CROSS_TRACK, double(fdiv(M<G>::abs(ln * (xg[FD_X_E] - from[FD_WP_EAST]) - le * (xg[FD_X_N] - from[FD_WP_NORTH])), len)));
+                    }
                 }
                 flown += 1;
             }
@@ -755,13 +857,26 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         for (int s = 0; s < iters; ++s) {
             set_air_mass();
             set_air_carried(f);
-            if (!guide(f.x0, [&]() { return derived_fast(f); }, advance)) {
+            if constexpr (LM) {
+                if (advance) estimate(s); else estimate_stored();
+                position(s, advance, f.x0);
+            }
+            if (!guide(seen_by_guidance(f.x0), [&]() {
+                    if constexpr (LM) { if (ea.feedback != FD_LQG_TRUTH) return derived<G>(xg); }
+                    return derived_fast(f);
+                }, advance)) {
                 if (!advance) return;                            // controls only: a complete lane writes nothing at all
                 break;
             }
-            if constexpr (LQG) estimate(s);
+            if constexpr (LQG && !LM) estimate(s);
             surf = control(advance);
-            if constexpr (LQG) account(surf);
+            if constexpr (LM) {
+                if (advance) {
+                    account(surf);
+                    if (ea.feedback != FD_LQG_TRUTH)             // x is the true state again, f.x0 never was anything else
+                        mission_stats(f.x0, fast::sqrt(__builtin_fmaf(f.x0[3], f.x0[3], __builtin_fmaf(f.x0[4], f.x0[4], f.x0[5] * f.x0[5]))), -f.x0[2]);
+                }
+            } else if constexpr (LQG) account(surf);
             if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
@@ -773,13 +888,23 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         for (int s = 0; s < iters; ++s) {
             set_air_mass();
             set_air_stored();
-            if (!guide(x, [&]() { return derived<S>(x); }, advance)) {
+            if constexpr (LM) {
+                if (advance) estimate(s); else estimate_stored();
+                position(s, advance, x);
+            }
+            if (!guide(seen_by_guidance(x), [&]() { return derived<S>(seen_by_guidance(x)); }, advance)) {
                 if (!advance) return;
                 break;
             }
-            if constexpr (LQG) estimate(s);
+            if constexpr (LQG && !LM) estimate(s);
             surf = control(advance);
-            if constexpr (LQG) account(surf);
+            if constexpr (LM) {
+                if (advance) {
+                    account(surf);
+                    if (ea.feedback != FD_LQG_TRUTH)
+                        mission_stats(x, M<S>::sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]), -x[2]);
+                }
+            } else if constexpr (LQG) account(surf);
             if constexpr (MISSION) { if (!advance) break; }
             Controls<T> C;
             C.set(P, surf.elevator, surf.aileron, surf.rudder, surf.throttle);
@@ -788,6 +913,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             if constexpr (!MISSION) move_refs();
         }
     }
+    if constexpr (LM) { if (idx >= m.n_wp) restore(); }           // left the loop complete, after the law's input went into x
     // the addresses of the stores below are recomputed from a lane index the compiler cannot equate with `i`, so that none of
     // them lives across the step loop
     int64_t ie = i;
@@ -796,6 +922,12 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
         if (n_steps > 0) {
             m.wp_idx[ie] = idx;
             if (m.reached_total) m.reached_total[ie] += reached;
+            if constexpr (LM) {                                  // the measurement and the filters of a completing step stand
+#pragma unroll
+                for (int j = 0; j < FD_NSKX; ++j) ea.xhat[int64_t(j) * n + ie] = double(lg.get(SG_XHAT + j));
+#pragma unroll
+                for (int k = 0; k < 2; ++k) ea.phat[int64_t(k) * n + ie] = ld.get(SD_PHAT + k);
+            }
             if (flown == 0) return;                              // complete before its first step here: nothing else of the lane changes
             if (m.steps_flown) m.steps_flown[ie] += flown;
             ref[int64_t(FD_SVR_SPEED) * n + ie] = ld.get(SD_REF + FD_SVR_SPEED);
@@ -824,8 +956,10 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             for (int k = 0; k < 3; ++k) wa.rows[int64_t(FD_SW_GUST_N + k) * n + ie] = ld.get(SD_GUST + k);
         }
         if constexpr (LQG) {
+            if constexpr (!LM) {
 #pragma unroll
-            for (int j = 0; j < FD_NSKX; ++j) ea.xhat[int64_t(j) * n + ie] = double(lg.get(SG_XHAT + j));
+                for (int j = 0; j < FD_NSKX; ++j) ea.xhat[int64_t(j) * n + ie] = double(lg.get(SG_XHAT + j));
+            }
 #pragma unroll
             for (int k = 0; k < FD_NU; ++k) ea.du_prev[int64_t(k) * n + ie] = double(lg.get(SG_DU + k));
         }
@@ -887,6 +1021,32 @@ servo_lqg_step_kernel(S* __restrict__ xs, const double* __restrict__ x0, const d
 {
     servo_step_body<S, T, false>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, NoMission{},
                                  NoWind{}, e);
+}
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_lqg_mission_kernel(S* __restrict__ xs, const double* __restrict__ x0, const double* __restrict__ u0, const double* __restrict__ K,
+                         double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits, const uint8_t* __restrict__ type,
+                         const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out,
+                         int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Mission m, EstimatorPos e)
+{
+    servo_step_body<S, T, true>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, m, NoWind{}, e);
+}
+
+// refusals in launch_mission's order, then launch_lqg_step's; the two words of pos are the host layer's to check
+template <typename S, typename T>
+int launch_lqg_mission(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ, const double* limits,
+                       const Mission& m, const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps,
+                       S* surf_out, int32_t* sat_steps, double* err_out, const EstimatorPos& e, void* stream)
+{
+    if (n_steps < 0 || m.n_wp < 1 || m.n_wp > FD_MAX_WAYPOINTS) return FDYN_ERR_BAD_SIZE;
+    FD_CHECK_FLEET(n, n_types, LB)
+    if (!x || !x0 || !u0 || !K || !ref || !integ || !limits || !params || !m.wp_idx || !m.consts || !m.wps) return FDYN_ERR_NULL;
+    if (!e.F || !e.sigma || !e.xhat || !e.du_prev || !e.pos || !e.phat) return FDYN_ERR_NULL;
+    if (e.feedback != FD_LQG_ESTIMATE && e.feedback != FD_LQG_MEASUREMENT && e.feedback != FD_LQG_TRUTH) return FDYN_ERR_BAD_SIZE;
+    if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
+    return launch<LB>(servo_lqg_mission_kernel<S, T>, n, stream, x, x0, u0, K, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                      surf_out, sat_steps, err_out, m, e);
 }
 
 // dyn_lds: the f64 step with the filter in dynamic LDS (fdyn_servo_lqg_step_f64_lds)
@@ -1041,5 +1201,26 @@ FD_SERVO_LQG(mixed, double, float, false)
 FD_SERVO_LQG(f32, float, float, false)
 FD_SERVO_LQG(f64_lds, double, double, true)
 #undef FD_SERVO_LQG
+
+#define FD_SERVO_LQG_MISSION(NAME, S, T)                                                                                              \
+    int fdyn_servo_lqg_mission_##NAME(S* x, const double* x0, const double* u0, const double* K, double* ref, double* integ,          \
+                                      const double* limits, int32_t* wp_idx, const double* consts, const double* wps, int n_wp,       \
+                                      const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps,      \
+                                      S* surf_out, int32_t* sat_steps, double* err_out, int32_t* reached_total, int32_t* steps_flown, \
+                                      double* stats, const double* F, const double* sigma, double* xhat, double* du_prev,            \
+                                      uint64_t seed, const int32_t* step, const double* z, int feedback, double* err_est,            \
+                                      double* err_meas, double* chatter, double* meas_out, const double* pos, double* phat,          \
+                                      double* err_pos, void* stream)                                                                  \
+    {                                                                                                                                  \
+        EstimatorPos e;                                                                                                                \
+        static_cast<Estimator&>(e) = Estimator{ F, sigma, xhat, du_prev, seed, step, z, feedback, err_est, err_meas, chatter, meas_out }; \
+        e.pos = pos; e.phat = phat; e.err_pos = err_pos;                                                                               \
+        return launch_lqg_mission<S, T>(x, x0, u0, K, ref, integ, limits, Mission{ wp_idx, consts, wps, n_wp, reached_total, steps_flown, stats }, \
+                                        type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, e, stream);               \
+    }
+FD_SERVO_LQG_MISSION(f64, double, double)
+FD_SERVO_LQG_MISSION(mixed, double, float)
+FD_SERVO_LQG_MISSION(f32, float, float)
+#undef FD_SERVO_LQG_MISSION
 
 }  // extern "C"

@@ -23,6 +23,7 @@ class BatchedSixDOF:
     _servo = servo = None        # the last design_servo() and the ServoState it started
     servo_mission = None         # the last start_servo_mission()
     _servo_kalman = servo_lqg = None    # the last design_servo_kalman() and the ServoLqgState it started
+    servo_position = servo_position_state = None    # the last start_servo_lqg_mission(): ServoPositionFilter, ServoLqgMissionState
 
     def __init__(self, n: int, precision: str = "f64", types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, device=None):
@@ -243,6 +244,37 @@ class BatchedSixDOF:
         kalman = self._servo_kalman
         SL.lqg_step_into(self.precision, self.x, design, kalman, self.servo, self.servo_lqg, self.params, self.type_index, kalman.dt,
                          n_steps, feedback, z, self.u, self._saturated_steps(), self.servo.err)
+        self.time += kalman.dt * n_steps
+
+    # waypoint missions on the servo's estimate (hcrl_amd.servo_lqg_mission): the mission's guidance fed by the filter and by a
+    # filtered position measurement
+    def start_servo_lqg_mission(self, waypoints, guidance_type: str = "PP", acceptance_radius: Optional[float] = None,
+                                on_complete: str = "freeze", flight_config=None, sigma_pos: Optional[float] = None,
+                                gain: Optional[float] = None, rate_pos: Optional[float] = None):
+        """start_servo_mission, and the position filter of fly_servo_lqg_mission (`servo_position`: ServoPositionFilter at the
+        sensor layer's position noise and position_gain's gain unless given; `servo_position_state`: phat at the fleet's north and
+        east).  Needs design_servo() and design_servo_kalman() first.  Returns the ServoMission."""
+        from . import servo_lqg_mission as SM
+        if self._servo_kalman is None:
+            raise ValueError(f"{type(self).__name__}.start_servo_lqg_mission: the fleet has no servo filter; call .design_servo_kalman() first")
+        mission = self.start_servo_mission(waypoints, guidance_type, acceptance_radius, on_complete, flight_config)
+        self.servo_position = SM.ServoPositionFilter.make(self.device, sigma_pos, gain, SM.DEFAULT_RATE_POS if rate_pos is None else rate_pos,
+                                                          self._servo_kalman.dt)
+        self.servo_position_state = SM.ServoLqgMissionState.start(self.x)
+        return mission
+
+    def fly_servo_lqg_mission(self, n_steps: int = 1, feedback: str = "estimate", z=None):
+        """n_steps x {measure -> Kalman update -> position filter -> mission update -> guidance on the estimate -> the control step
+        of step_servo_lqg -> one RK4 of the filter's dt} in ONE launch; feedback and the estimator's words as step_servo_lqg, z
+        [n_steps][12][N] (the last two words: the north and east position normals).  `servo_mission.stats` are the TRUE state's."""
+        from . import servo_lqg_mission as SM
+        design = self._need_servo("fly_servo_lqg_mission")
+        if self.servo_mission is None or self.servo_position is None:
+            raise ValueError(f"{type(self).__name__}.fly_servo_lqg_mission: the fleet has no mission on the estimate; call .start_servo_lqg_mission() first")
+        kalman = self._servo_kalman
+        SM.lqg_mission_into(self.precision, self.x, design, kalman, self.servo, self.servo_lqg, self.servo_mission, self.servo_position,
+                            self.servo_position_state, self.params, self.type_index, kalman.dt, n_steps, feedback, z, self.u,
+                            self._saturated_steps(), self.servo.err)
         self.time += kalman.dt * n_steps
 
     # LQG (hcrl_amd.lqg): the estimator beside the LQR, and the output-feedback loop on noisy measurements

@@ -37,4 +37,6 @@ globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_wind.h")))
 globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_lqg.h")))
 # and the rows of the servo's flight-mode report (FD_SMO_*, FD_NSMO_*)
 globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_modes.h")))
+# and the normals and the position-filter words of the servo's missions on noisy sensors (FD_NSKZ, FD_NSPF, FD_SPF_*)
+globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_lqg_mission.h")))
 __all__ = [k for k in globals() if k.startswith("FD_")]

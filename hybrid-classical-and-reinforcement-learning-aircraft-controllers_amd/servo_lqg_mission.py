@@ -1,0 +1,135 @@
+"""Waypoint missions on the LQ servo ON NOISY SENSORS: `hcrl_amd.servo`'s mission flown on `hcrl_amd.servo_lqg`'s estimate, with a
+filtered north / east position measurement for the guidance -- one launch of fdyn_servo_lqg_mission_* per n control steps
+(include/fdyn_servo_lqg_mission.h): measure, Kalman filter, position filter, mission update, guidance, servo law, RK4.
+
+    fleet = BatchedSixDOF(65536, "mixed", types=("rc_plane", "cessna"), type_index=idx)
+    fleet.trim(20.0, altitude=100.0)
+    fleet.design_servo()
+    fleet.design_servo_kalman(dt=0.01)
+    mission = fleet.start_servo_lqg_mission(square_mission(300.0, 100.0, 20.0))      # position filter at its default gain
+    while not bool(fleet.servo_mission_complete().all()):
+        fleet.fly_servo_lqg_mission(100)             # feedback="estimate" | "measurement" | "truth"
+
+The position filter is a random walk driven by the estimated ground velocity: p+ = p + dt v, p = p+ + g (y_p - p+), one gain g
+for both axes and the whole fleet (`position_gain`: the steady-state Kalman gain of that scalar model).  The mission statistics
+stay those of the TRUE state.
+
+Nothing here synchronises with the device.
+"""
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib, layout as L
+from . import servo as SV
+from . import servo_lqg as SL
+from .lqg import FEEDBACK
+from .sensors import noise_block
+
+DEFAULT_RATE_POS = 0.5                      # s_p, m per sqrt(s): the random walk the position filter allows beside dt v
+
+
+def default_sigma_pos(noise_config: Optional[dict] = None) -> float:
+    """The sensor layer's standard deviation of a GPS position measurement, m (`gps_position_stddev`, 1.0 by default)."""
+    return float(noise_block(noise_config)[L.FD_SN_GPS_POS])
+
+
+def position_gain(sigma_pos: Optional[float] = None, rate_pos: float = DEFAULT_RATE_POS, dt: float = 0.01) -> float:
+    """The steady-state Kalman gain of a random-walk position with measurement variance r = sigma_pos^2 and process variance
+    q = rate_pos^2 dt: P- = (q + sqrt(q^2 + 4 q r)) / 2, g = P- / (P- + r).  0.0488 at the defaults and dt 0.01; 1 for r = 0."""
+    sigma_pos = default_sigma_pos() if sigma_pos is None else float(sigma_pos)
+    r, q = sigma_pos * sigma_pos, float(rate_pos) * float(rate_pos) * float(dt)
+    if not (math.isfinite(r) and math.isfinite(q) and q > 0.0 and sigma_pos >= 0.0):
+        raise ValueError("position_gain: sigma_pos must be finite and >= 0, rate_pos and dt finite and > 0")
+    pm = (q + math.sqrt(q * q + 4.0 * q * r)) / 2.0
+    return pm / (pm + r)
+
+
+@dataclass
+class ServoPositionFilter:
+    """The two words of `pos` (FD_SPF_*) and their device copy.  The C entry cannot read them; they are checked HERE."""
+    sigma: float                            # standard deviation of the north / east measurement, m
+    gain: float                             # g in (0, 1]
+    words: torch.Tensor                     # [FD_NSPF] float64 on the device
+
+    @classmethod
+    def make(cls, device, sigma_pos: Optional[float] = None, gain: Optional[float] = None, rate_pos: float = DEFAULT_RATE_POS,
+             dt: float = 0.01) -> "ServoPositionFilter":
+        """sigma_pos None: the sensor layer's default; gain None: position_gain(sigma_pos, rate_pos, dt)."""
+        sigma = default_sigma_pos() if sigma_pos is None else float(sigma_pos)
+        check_position_words(sigma, 1.0 if gain is None else float(gain))
+        g = position_gain(sigma, rate_pos, dt) if gain is None else float(gain)
+        words = np.zeros(L.FD_NSPF, np.float64)
+        words[L.FD_SPF_SIGMA], words[L.FD_SPF_GAIN] = sigma, g
+        return cls(sigma, g, torch.as_tensor(words, device=device))
+
+
+def check_position_words(sigma: float, gain: float):
+    """What include/fdyn_servo_lqg_mission.h leaves to the host: the refusal the C-ABI would give as FDYN_ERR_BAD_SIZE."""
+    if not (math.isfinite(sigma) and sigma >= 0.0):
+        raise _lib.FdynError(f"fdyn_servo_lqg_mission: bad size argument (position sigma {sigma}: finite and >= 0)")
+    if not (math.isfinite(gain) and 0.0 < gain <= 1.0):
+        raise _lib.FdynError(f"fdyn_servo_lqg_mission: bad size argument (position gain {gain}: in (0, 1])")
+
+
+@dataclass
+class ServoLqgMissionState:
+    """What the position filter carries between launches, on the device."""
+    phat: torch.Tensor                      # [2][n] float64: the estimate of (north, east)
+    err_pos: torch.Tensor                   # [2][n] float64: sums of |phat - p|^2 and of |y_p - p|^2
+
+    @classmethod
+    def start(cls, x: torch.Tensor) -> "ServoLqgMissionState":
+        """phat = the north and east of the state x [12][n]; accumulators zero."""
+        out = cls(torch.empty((2, int(x.shape[1])), dtype=torch.float64, device=x.device),
+                  torch.zeros((2, int(x.shape[1])), dtype=torch.float64, device=x.device))
+        out.reset(x)
+        return out
+
+    def reset(self, x: torch.Tensor):
+        self.phat[0] = x[L.FD_X_N].to(torch.float64)
+        self.phat[1] = x[L.FD_X_E].to(torch.float64)
+        self.err_pos.zero_()
+
+    def error_ratio(self) -> torch.Tensor:
+        """[n]: err_pos[0] / err_pos[1], the filtered position's squared error over the raw measurement's."""
+        return self.err_pos[0] / self.err_pos[1]
+
+
+def lqg_mission_into(precision: str, x: torch.Tensor, design: SV.ServoDesign, kalman: SL.ServoKalmanDesign, state: SV.ServoState,
+                     lqg_state: SL.ServoLqgState, mission: SV.ServoMission, pos: ServoPositionFilter, pos_state: ServoLqgMissionState,
+                     params: torch.Tensor, type_index: Optional[torch.Tensor], dt: float, n_steps: int, feedback="estimate",
+                     z: Optional[torch.Tensor] = None, surf_out: Optional[torch.Tensor] = None, sat_steps: Optional[torch.Tensor] = None,
+                     err_out: Optional[torch.Tensor] = None, accumulate: bool = True):
+    """One launch of fdyn_servo_lqg_mission_<precision>: x [12][n] in the precision's storage type, advanced in place with the servo
+    state, the estimator's words, the mission's words and the position filter's; then the step word advances by n_steps (on the
+    stream).  n_steps = 0 writes surf_out alone.  z: None = in-kernel draws, or [n_steps][12][n] float64 standard normals."""
+    if design.x0 is None or design.u0 is None:
+        raise ValueError("the servo design carries no trim point (x0, u0)")
+    if kalman.sigma is None:
+        raise ValueError("the Kalman design carries no measurement noise (sigma)")
+    n = int(x.shape[1])
+    if (x.dtype != _lib.state_dtype(precision) or design.n != n or kalman.n != n or state.n != n or mission.n != n
+            or int(lqg_state.xhat.shape[1]) != n or int(pos_state.phat.shape[1]) != n):
+        raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and the designs, the states and the mission of that fleet")
+    check_position_words(pos.sigma, pos.gain)
+    fb = FEEDBACK[feedback] if isinstance(feedback, str) else int(feedback)
+    if z is not None and (tuple(z.shape) != (int(n_steps), L.FD_NSKZ, n) or z.dtype != torch.float64 or not z.is_contiguous()):
+        raise ValueError(f"z must be contiguous float64 [{int(n_steps)}][{L.FD_NSKZ}][{n}]")
+    acc = (lqg_state.err_est, lqg_state.err_meas, lqg_state.chatter, lqg_state.meas) if accumulate else (None, None, None, None)
+    rc = getattr(_lib.load(), f"fdyn_servo_lqg_mission_{precision}")(
+        _lib.ptr(x), _lib.ptr(design.x0), _lib.ptr(design.u0), _lib.ptr(design.K), _lib.ptr(state.ref), _lib.ptr(state.integ),
+        _lib.ptr(state.limits), _lib.ptr(mission.wp_idx), _lib.ptr(mission.consts), _lib.ptr(mission.wps), mission.n_wp,
+        _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps), _lib.ptr(surf_out), _lib.ptr(sat_steps),
+        _lib.ptr(err_out), _lib.ptr(mission.reached_total), _lib.ptr(mission.steps_flown), _lib.ptr(mission.stats),
+        _lib.ptr(kalman.F), _lib.ptr(kalman.sigma), _lib.ptr(lqg_state.xhat), _lib.ptr(lqg_state.du_prev),
+        int(lqg_state.seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(lqg_state.step), _lib.ptr(z), fb, *(_lib.ptr(t) for t in acc),
+        _lib.ptr(pos.words), _lib.ptr(pos_state.phat), _lib.ptr(pos_state.err_pos if accumulate else None), _lib.current_stream())
+    _lib.check(rc, "fdyn_servo_lqg_mission")
+    if n_steps > 0:
+        if lqg_state.step is not None:                   # None: no step word (the kernel reads 0)
+            lqg_state.step.add_(int(n_steps))
+        lqg_state.steps_accumulated += int(n_steps)

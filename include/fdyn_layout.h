@@ -177,7 +177,10 @@ enum {
  * layouts").  Env kernels, counter (env, episode, step, word): the IC and command record FD_PHX_RESET..+3, the random-walk command
  * increment FD_PHX_RANDOM_WALK, the randomisation rows FD_PHX_DR_RESET..+2, the initial gust FD_PHX_DR_GUST0, the gust update
  * FD_PHX_GUST.  Row kernels, counter (row low, row high, step, word): the policy's action noise FD_PHX_ACTION, the five blocks of
- * a sensor update FD_PHX_SENSOR..+4, the two blocks of an LQG step's measurement noise FD_PHX_LQG..+1.                        */
+ * a sensor update FD_PHX_SENSOR..+4, the two blocks of an LQG step's measurement noise FD_PHX_LQG..+1.  The servo's own words
+ * live in the headers of their entry points: FD_PHX_SERVO_GUST (fdyn_wind.h) and the three blocks FD_PHX_SERVO_LQG..+2
+ * (fdyn_servo_lqg.h), of whose twelve normals fdyn_servo_lqg_step_* uses ten; words 10 and 11 are the north and east position
+ * noise of fdyn_servo_lqg_mission_* (fdyn_servo_lqg_mission.h).                                                              */
 enum {
     FD_PHX_RESET = 0, FD_PHX_RANDOM_WALK = 7, FD_PHX_DR_RESET = 16, FD_PHX_DR_GUST0 = 19, FD_PHX_GUST = 20,
     FD_PHX_ACTION = 0x51, FD_PHX_SENSOR = 0x60, FD_PHX_LQG = 0x70
