@@ -70,6 +70,9 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_modes.h"))
 # and the servo's waypoint missions on noisy sensors (include/fdyn_servo_lqg_mission.h): a ninth
 with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_lqg_mission.h")) as _f:
     SERVO_LQG_MISSION_SIGNATURES = _parse_header(_f.read(), "include/fdyn_servo_lqg_mission.h")[0]
+# and the servo's predicted covariances (include/fdyn_servo_covariance.h): a tenth
+with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_covariance.h")) as _f:
+    SERVO_COVARIANCE_SIGNATURES = _parse_header(_f.read(), "include/fdyn_servo_covariance.h")[0]
 
 _lib = None
 
@@ -95,7 +98,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *MODES_SIGNATURES.items(), *SERVO_SIGNATURES.items(), *MISSION_SIGNATURES.items(),
                                   *WIND_SIGNATURES.items(), *SERVO_LQG_SIGNATURES.items(), *SERVO_MARGIN_SIGNATURES.items(),
-                                  *SERVO_MODES_SIGNATURES.items(), *SERVO_LQG_MISSION_SIGNATURES.items()):
+                                  *SERVO_MODES_SIGNATURES.items(), *SERVO_LQG_MISSION_SIGNATURES.items(),
+                                  *SERVO_COVARIANCE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
         if lib.fdyn_abi_version() != FDYN_ABI_VERSION:

@@ -347,6 +347,20 @@ class BatchedSixDOF:
         A, B = T.linearize_at_trim(res, self.params, self.type_index, trim_scales if scales is None else scales)
         return self._servo.modes(A, B)
 
+    def servo_covariance(self, feedback: str = "estimate", sigma=None, process_rates=None):
+        """ServoCovariance of every aircraft's servo loop as `step_servo_lqg(feedback=...)` flies it in its linear region, at the
+        filter's dt: the predicted steady-state variances of the state, the estimate, the tracking errors, the integrators, the
+        controls and their step-to-step change (rms_tracking(), chatter(), headroom(u0), ...).  sigma: None = the measurement noise
+        `step_servo_lqg` applies (the filter design's `sigma`: the noise it was designed for when that is shared by the fleet, the
+        sensor layer's defaults when it was designed on per-aircraft noise); process_rates: None = no process noise acts, as in the
+        flights.  Needs design_servo() and
+        design_servo_kalman() first.  The fleet's state is not touched."""
+        from . import servo_covariance as SC
+        for design, lacks, call in ((self._servo, "stabilising servo gain", "design_servo()"), (self._servo_kalman, "stable servo filter", "design_servo_kalman(dt)")):
+            if design is None:
+                raise ValueError(f"{type(self).__name__}.servo_covariance: {self.n} of {self.n} aircraft have no certified {lacks} (call .{call} first)")
+        return SC.servo_covariance(self._servo, self._servo_kalman, self._servo.x0, None, sigma, process_rates, feedback)
+
     # Flight modes (hcrl_amd.modes): where the poles are
     def modes(self, design=None, scales=None):
         """FleetModes of every aircraft linearised at the fleet's current trim (the last `.trim(...)`): the open-loop poles, or

@@ -39,4 +39,6 @@ globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_lqg.h"))
 globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_modes.h")))
 # and the normals and the position-filter words of the servo's missions on noisy sensors (FD_NSKZ, FD_NSPF, FD_SPF_*)
 globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_lqg_mission.h")))
+# and the rows and status bits of the servo's predicted covariances (FD_SCV_*, FD_SCC_*, FD_NSCV, FD_NSCC)
+globals().update(_parse(os.path.join(os.path.dirname(_HDR), "fdyn_servo_covariance.h")))
 __all__ = [k for k in globals() if k.startswith("FD_")]
