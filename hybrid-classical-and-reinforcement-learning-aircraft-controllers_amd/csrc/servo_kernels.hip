@@ -29,6 +29,11 @@
 //                     MISSION and an estimator both on.  The estimator runs FIRST here; a fixed-gain filter on a north / east
 //                     position measurement (the two spare normals of the estimator's draw) gives the guidance its position, and the
 //                     statistics stay on the true state.  Everything it adds is behind the EstimatorPos argument type.
+// fdyn_servo_sched_step_*, fdyn_servo_sched_mission_*  the servo gain-scheduled over airspeed in flight
+//                     (include/fdyn_servo_sched.h): the body a fifth time, behind the Schedule argument type.  The law reads its
+//                     trim point and gains from LDS columns every step anyway; in front of each control step those columns are
+//                     rewritten from the two nodes of the aircraft's table that bracket its airspeed (or its speed command).
+//                     The table stays in global memory, [node][word][lane], so that a wave reads each word in one burst.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fdyn_fleet.hpp"
@@ -42,6 +47,7 @@
 #include "../../include/fdyn_wind.h"
 #include "../../include/fdyn_servo_lqg.h"
 #include "../../include/fdyn_servo_lqg_mission.h"
+#include "../../include/fdyn_servo_sched.h"
 
 using namespace fdyn;
 
@@ -293,6 +299,9 @@ struct Estimator {
 struct EstimatorDynLds : Estimator {};
 // what fdyn_servo_lqg_mission_* add to the estimator (include/fdyn_servo_lqg_mission.h): the position filter of the guidance
 struct EstimatorPos : Estimator { const double* pos /*[2]*/; double* phat /*[2][n]*/; double* err_pos /*[2][n]*/; };
+// What fdyn_servo_sched_* add (include/fdyn_servo_sched.h); NoSchedule is the one design of x0, u0, K.
+struct NoSchedule {};
+struct Schedule { const double* table /*[n_nodes][FD_NSS][n]*/; int n_nodes; int on; double* sigma_out /*[2][n]*/; };
 constexpr int DYN_F_BYTES = FD_NSKF * 64 * int(sizeof(double));
 // the ten estimated words inside x, their angles, and where the trim's word sits among the fp64 columns (z0, psi0 behind SD_LQG)
 __device__ constexpr int EST_W[FD_NSKX] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_D, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL, FD_X_YAW };
@@ -323,12 +332,14 @@ FD_DEV void servo_lqg_normals(uint64_t seed, int64_t i, uint32_t step, float (&z
 // duration of the call while the true ones wait in `keep`.
 // With MISSION and an EstimatorPos (LM) the order of a control step changes: estimate, position filter, then the guidance on `xg`
 // (the law's input with the filtered position), the law, `account`, and the statistics on the true state.
-template <typename S, typename T, bool MISSION, typename MA, typename WA = NoWind, typename EA = NoEstimator>
+// With a Schedule (SCHED) x0, u0 and K are not read: `reschedule`, in front of the law, fills the columns the prologue fills
+// otherwise, and two more fp64 columns hold the sigma they were built from and the table position.
+template <typename S, typename T, bool MISSION, typename MA, typename WA = NoWind, typename EA = NoEstimator, typename SA = NoSchedule>
 FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __restrict__ x0 /*[12][n]*/, const double* __restrict__ u0 /*[4][n]*/,
                             const double* __restrict__ K /*[26][n]*/, double* __restrict__ ref /*[5][n]*/, double* __restrict__ integ /*[3][n]*/,
                             const double* __restrict__ limits /*[3]*/, const uint8_t* __restrict__ type, const double* __restrict__ params,
                             int n_types, int64_t n, S dt, int n_steps, S* __restrict__ surf_out /*[4][n]*/, int32_t* __restrict__ sat_steps,
-                            double* __restrict__ err_out /*[3][n]*/, const MA& m, const WA& wa = WA{}, const EA& ea = EA{})
+                            double* __restrict__ err_out /*[3][n]*/, const MA& m, const WA& wa = WA{}, const EA& ea = EA{}, const SA& sa = SA{})
 {
     using G = typename GlueOf<S, T>::type;
     constexpr bool FAST = sizeof(T) == 4;
@@ -336,6 +347,8 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     constexpr bool LQG = !__is_same(EA, NoEstimator);
     constexpr bool LM = __is_same(EA, EstimatorPos);                             // the mission on the estimate
     static_assert(!LM || (MISSION && !WINDY), "the position filter belongs to the still-air mission");
+    constexpr bool SCHED = !__is_same(SA, NoSchedule);
+    static_assert(!SCHED || (!WINDY && !LQG), "the schedule is flown in still air on the true state");
     constexpr int NZ = LM ? FD_NSKZ : FD_NSKX;                                   // normals per step of a replayed z
     constexpr bool F_DYN = __is_same(EA, EstimatorDynLds);                       // fp64 glue: the filter's words in dynamic LDS
     constexpr bool F_LDS = LQG && sizeof(G) == 4;                                // the filter's words in LDS (fp32 glue) or read from F
@@ -344,7 +357,8 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     constexpr int SD_STAT = SD_N, SD_GUST = MISSION ? SD_N + FD_NMST : SD_N;      // WINDY: g [3], then A, B, then W [3]
     constexpr int SD_WIND = SD_GUST + 5, SD_LQG = WINDY ? SD_WIND + 3 : SD_GUST; // LQG: the trim's z and psi
     constexpr int SD_KEEP = SD_LQG + 2, SD_PHAT = SD_KEEP + FD_NSKX;             // and the true ten words while the law reads x_f; LM: phat [2]
-    constexpr int SD_WORDS = LM ? SD_PHAT + 2 : (LQG ? SD_PHAT : SD_LQG);
+    constexpr int SD_SIG = SD_LQG, SD_POS = SD_SIG + 1;                          // SCHED: the sigma the law's columns hold, the position
+    constexpr int SD_WORDS = SCHED ? SD_POS + 1 : (LM ? SD_PHAT + 2 : (LQG ? SD_PHAT : SD_LQG));
     constexpr int SG_AIR = SG_N, SG_XHAT = WINDY ? SG_N + 3 : SG_N;              // WINDY: W + g [3]; LQG: xhat [10], du_prev [4], F [120]
     constexpr int SG_DU = SG_XHAT + FD_NSKX, SG_F = SG_DU + FD_NU;
     constexpr int SG_WORDS = LQG ? (F_LDS ? SG_F + FD_NSKF : SG_F) : SG_XHAT;
@@ -376,21 +390,27 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     }
     {
 #pragma clang fp contract(off)
-        constexpr int W[8] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL };
+        if constexpr (SCHED) {
+            ld.set(SD_POS, -1.0);                                // no position is negative: the law's columns hold nothing yet
+        } else {
+            constexpr int W[8] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL };
 #pragma unroll
-        for (int j = 0; j < 8; ++j) ld.set(SD_X0 + j, x0[W[j] * n + i]);
-        const double tu = x0[FD_X_U * n + i], tw = x0[FD_X_W * n + i];
-        const double V0 = ::sqrt(tu * tu + tw * tw);
-        const bool moving = V0 > 0.0;                            // false only for a lane whose design was refused (K = 0)
-        ld.set(SD_V0, V0);
-        lg.set(SG_CU, G(moving ? tu / V0 : 0.0));
-        lg.set(SG_CW, G(moving ? tw / V0 : 0.0));
+            for (int j = 0; j < 8; ++j) ld.set(SD_X0 + j, x0[W[j] * n + i]);
+            const double tu = x0[FD_X_U * n + i], tw = x0[FD_X_W * n + i];
+            const double V0 = ::sqrt(tu * tu + tw * tw);
+            const bool moving = V0 > 0.0;                        // false only for a lane whose design was refused (K = 0)
+            ld.set(SD_V0, V0);
+            lg.set(SG_CU, G(moving ? tu / V0 : 0.0));
+            lg.set(SG_CW, G(moving ? tw / V0 : 0.0));
+        }
 #pragma unroll
         for (int k = 0; k < FD_NSVR; ++k) ld.set(SD_REF + k, ref[int64_t(k) * n + i]);
+        if constexpr (!SCHED) {
 #pragma unroll
-        for (int k = 0; k < FD_NSVK; ++k) lg.set(SG_K + k, G(K[int64_t(k) * n + i]));
+            for (int k = 0; k < FD_NSVK; ++k) lg.set(SG_K + k, G(K[int64_t(k) * n + i]));
 #pragma unroll
-        for (int k = 0; k < FD_NU; ++k) lg.set(SG_U0 + k, G(u0[int64_t(k) * n + i]));
+            for (int k = 0; k < FD_NU; ++k) lg.set(SG_U0 + k, G(u0[int64_t(k) * n + i]));
+        }
 #pragma unroll
         for (int k = 0; k < FD_NSVI; ++k) lg.set(SG_INT + k, G(integ[int64_t(k) * n + i]));
         if constexpr (WINDY) {
@@ -487,6 +507,69 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             const double ga = ld.get(SD_GUST + 3), gb = ld.get(SD_GUST + 4);
 #pragma unroll
             for (int k = 0; k < 3; ++k) ld.set(SD_GUST + k, gust_update(ld.get(SD_GUST + k), ga, gb, zn[k]));
+        }
+    };
+
+    // SCHED, steps 0a-0c (include/fdyn_servo_sched.h): the law's columns from the two nodes that bracket sigma.  Skipped when sigma
+    // is bitwise the one the columns were built from (on the command: nearly every step); the columns are then what this would
+    // write.  Eight words in flight at a time, and everything it computes is dead when it returns.
+    auto reschedule = [&]() {
+        if constexpr (SCHED) {
+#pragma clang fp contract(off)
+            asm volatile("" ::: "memory");
+            double sg;
+            if (sa.on == FD_SCHED_ON_COMMAND) sg = ld.get(SD_REF + FD_SVR_SPEED);
+            else sg = double(M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]));
+            if (ld.get(SD_POS) >= 0.0 && __double_as_longlong(sg) == __double_as_longlong(ld.get(SD_SIG))) return;
+            // the lane index and the row stride made opaque, as the estimator's: none of these addresses lives across the RK4
+            int64_t il = i, nl = n;
+            asm volatile("" : "+v"(il), "+s"(nl));
+            const double* __restrict__ tb = sa.table + il;
+            const int last = sa.n_nodes - 1;
+            int k = 0;
+            double t = 0.0, pos = 0.0;
+            bool exact = true;                                   // a node's words as they are: below, above, NaN
+            const double v0 = tb[int64_t(FD_SS_V) * nl];
+            if (sg > v0) {
+                const double vl = tb[int64_t(last * FD_NSS + FD_SS_V) * nl];
+                if (sg >= vl) { k = last; pos = double(last); }
+                else {                                           // V_0 < sigma < V_last: last >= 1, and k + 1 <= last
+                    double vk = v0;
+#pragma unroll 1
+                    for (int j = 1; j < last; ++j) {
+                        const double vj = tb[int64_t(j * FD_NSS + FD_SS_V) * nl];
+                        if (vj <= sg) { k = j; vk = vj; }
+                    }
+                    const double vn = tb[int64_t((k + 1) * FD_NSS + FD_SS_V) * nl];
+                    t = (sg - vk) / (vn - vk);
+                    pos = double(k) + t;
+                    exact = false;
+                }
+            }
+            const double* __restrict__ lo = tb + int64_t(k * FD_NSS) * nl;
+            const double* __restrict__ hi = exact ? lo : lo + int64_t(FD_NSS) * nl;
+            auto word = [&](int r) -> double {
+                const double a = lo[int64_t(r) * nl], b = hi[int64_t(r) * nl];
+                return exact ? a : a + t * (b - a);
+            };
+#pragma unroll
+            for (int r = 0; r < 8; ++r) ld.set(SD_X0 + r, word(FD_SS_X0 + r));
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int r = 0; r < FD_NU; ++r) lg.set(SG_U0 + r, G(word(FD_SS_U0 + r)));
+#pragma unroll
+            for (int r = 0; r < FD_NSVK; ++r) {
+                if (r % 8 == 4) asm volatile("" ::: "memory");
+                lg.set(SG_K + r, G(word(FD_SS_K + r)));
+            }
+            const double tu = ld.get(SD_X0 + 0), tw = ld.get(SD_X0 + 1);
+            const double V0 = ::sqrt(tu * tu + tw * tw);
+            const bool moving = V0 > 0.0;
+            ld.set(SD_V0, V0);
+            lg.set(SG_CU, G(moving ? tu / V0 : 0.0));
+            lg.set(SG_CW, G(moving ? tw / V0 : 0.0));
+            ld.set(SD_SIG, sg);
+            ld.set(SD_POS, pos);
         }
     };
 
@@ -849,6 +932,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             else set_air_stored();
         }
         if constexpr (LQG) estimate_stored();
+        reschedule();
         surf = control(false);
     } else if constexpr (FAST) {
         FastRK f;
@@ -869,6 +953,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
                 break;
             }
             if constexpr (LQG && !LM) estimate(s);
+            reschedule();
             surf = control(advance);
             if constexpr (LM) {
                 if (advance) {
@@ -897,6 +982,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
                 break;
             }
             if constexpr (LQG && !LM) estimate(s);
+            reschedule();
             surf = control(advance);
             if constexpr (LM) {
                 if (advance) {
@@ -963,6 +1049,9 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
 #pragma unroll
             for (int k = 0; k < FD_NU; ++k) ea.du_prev[int64_t(k) * n + ie] = double(lg.get(SG_DU + k));
         }
+    }
+    if constexpr (SCHED) {
+        if (sa.sigma_out) { sa.sigma_out[ie] = ld.get(SD_SIG); sa.sigma_out[n + ie] = ld.get(SD_POS); }
     }
     if (surf_out) {                                              // the controls as applied: after set_controls' clip
         surf_out[FD_U_ELEVATOR * n + ie] = S(clipv<G>(surf.elevator, G(-1), G(1)));
@@ -1031,6 +1120,45 @@ servo_lqg_mission_kernel(S* __restrict__ xs, const double* __restrict__ x0, cons
                          int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Mission m, EstimatorPos e)
 {
     servo_step_body<S, T, true>(xs, x0, u0, K, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out, m, NoWind{}, e);
+}
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_sched_step_kernel(S* __restrict__ xs, double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits,
+                        const uint8_t* __restrict__ type, const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps,
+                        S* __restrict__ surf_out, int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Schedule sc)
+{
+    servo_step_body<S, T, false>(xs, nullptr, nullptr, nullptr, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps,
+                                 err_out, NoMission{}, NoWind{}, NoEstimator{}, sc);
+}
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_sched_mission_kernel(S* __restrict__ xs, double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits,
+                           const uint8_t* __restrict__ type, const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps,
+                           S* __restrict__ surf_out, int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Mission m, Schedule sc)
+{
+    servo_step_body<S, T, true>(xs, nullptr, nullptr, nullptr, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps,
+                                err_out, m, NoWind{}, NoEstimator{}, sc);
+}
+
+// `m`: NULL for fdyn_servo_sched_step_*.  Refusals in launch_step's / launch_mission's order, the schedule's own with the sizes
+template <typename S, typename T>
+int launch_sched(S* x, const Schedule& sc, double* ref, double* integ, const double* limits, const Mission* m, const uint8_t* type,
+                 const double* params, int n_types, int64_t n, double dt, int n_steps, S* surf_out, int32_t* sat_steps, double* err_out,
+                 void* stream)
+{
+    if (n_steps < 0 || (m && (m->n_wp < 1 || m->n_wp > FD_MAX_WAYPOINTS))) return FDYN_ERR_BAD_SIZE;
+    if (sc.n_nodes < 1 || sc.n_nodes > FD_MAX_SCHED_NODES) return FDYN_ERR_BAD_SIZE;
+    if (sc.on != FD_SCHED_ON_AIRSPEED && sc.on != FD_SCHED_ON_COMMAND) return FDYN_ERR_BAD_SIZE;
+    FD_CHECK_FLEET(n, n_types, LB)
+    if (!x || !sc.table || !ref || !integ || !limits || !params) return FDYN_ERR_NULL;
+    if (m && (!m->wp_idx || !m->consts || !m->wps)) return FDYN_ERR_NULL;
+    if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
+    if (!m) return launch<LB>(servo_sched_step_kernel<S, T>, n, stream, x, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                              surf_out, sat_steps, err_out, sc);
+    return launch<LB>(servo_sched_mission_kernel<S, T>, n, stream, x, ref, integ, limits, type, params, n_types, n, S(dt), n_steps,
+                      surf_out, sat_steps, err_out, *m, sc);
 }
 
 // refusals in launch_mission's order, then launch_lqg_step's; the two words of pos are the host layer's to check
@@ -1222,5 +1350,29 @@ FD_SERVO_LQG_MISSION(f64, double, double)
 FD_SERVO_LQG_MISSION(mixed, double, float)
 FD_SERVO_LQG_MISSION(f32, float, float)
 #undef FD_SERVO_LQG_MISSION
+
+#define FD_SERVO_SCHED(NAME, S, T)                                                                                                     \
+    int fdyn_servo_sched_step_##NAME(S* x, const double* sched, int n_nodes, int sched_on, double* ref, double* integ,                \
+                                     const double* limits, const uint8_t* type, const double* params, int n_types, int64_t n,         \
+                                     double dt, int n_steps, S* surf_out, int32_t* sat_steps, double* err_out, double* sigma_out,     \
+                                     void* stream)                                                                                     \
+    {                                                                                                                                  \
+        return launch_sched<S, T>(x, Schedule{ sched, n_nodes, sched_on, sigma_out }, ref, integ, limits, nullptr, type, params, n_types, n, \
+                                  dt, n_steps, surf_out, sat_steps, err_out, stream);                                                 \
+    }                                                                                                                                  \
+    int fdyn_servo_sched_mission_##NAME(S* x, const double* sched, int n_nodes, int sched_on, double* ref, double* integ,             \
+                                        const double* limits, int32_t* wp_idx, const double* consts, const double* wps, int n_wp,     \
+                                        const uint8_t* type, const double* params, int n_types, int64_t n, double dt, int n_steps,    \
+                                        S* surf_out, int32_t* sat_steps, double* err_out, int32_t* reached_total,                      \
+                                        int32_t* steps_flown, double* stats, double* sigma_out, void* stream)                          \
+    {                                                                                                                                  \
+        const Mission m{ wp_idx, consts, wps, n_wp, reached_total, steps_flown, stats };                                               \
+        return launch_sched<S, T>(x, Schedule{ sched, n_nodes, sched_on, sigma_out }, ref, integ, limits, &m, type, params, n_types, n, \
+                                  dt, n_steps, surf_out, sat_steps, err_out, stream);                                                 \
+    }
+FD_SERVO_SCHED(f64, double, double)
+FD_SERVO_SCHED(mixed, double, float)
+FD_SERVO_SCHED(f32, float, float)
+#undef FD_SERVO_SCHED
 
 }  // extern "C"

@@ -152,17 +152,47 @@ class BatchedSixDOF:
         self._need_servo("command_servo")
         self.servo.command(heading, speed, altitude)
 
-    def step_servo(self, n_steps: int = 1, dt: Optional[float] = None, wind=None):
+    def design_servo_schedule(self, airspeeds, climb=0.0, turn=0.0, altitude=None, heading=None, weights=None, scales=None,
+                              strict: bool = True):
+        """A table of LQ-servo designs over airspeed for every aircraft (hcrl_amd.servo_sched): ServoSchedule with table
+        [M][FD_NSS][N], for `step_servo(schedule=...)` and `fly_servo_mission(schedule=...)`.  airspeeds: M <= FD_MAX_SCHED_NODES
+        strictly increasing values, or [M][N]; climb (rad), turn (rad/s), altitude and heading: the other words of the nodes' flight
+        condition (altitude, heading None: those of the fleet's current trim, else 100 m and 0); weights and scales as design_servo
+        takes them (scales None: the multipliers of the current trim, if any).  One trim, one linearise and one design launch over
+        M N lanes.  ValueError for airspeeds that are not strictly increasing or for too many nodes; strict: also when a node has no
+        trim or no certified gain.  The fleet's state, trim and design are not touched."""
+        from . import servo_sched as SS
+        trim_scales = None
+        if self._trim is not None:
+            res, trim_scales = self._trim
+            altitude = -res.x0[L.FD_X_D] if altitude is None else altitude
+            heading = res.x0[L.FD_X_YAW] if heading is None else heading
+        out = SS.design_servo_schedule(airspeeds, self.n, self.params, self.type_index, climb, turn, 100.0 if altitude is None else altitude,
+                                       0.0 if heading is None else heading, weights, trim_scales if scales is None else scales, strict=False)
+        if strict:
+            out.require_ok(f"{type(self).__name__}.design_servo_schedule")
+        return out
+
+    def step_servo(self, n_steps: int = 1, dt: Optional[float] = None, wind=None, schedule=None, on: str = "airspeed"):
         """n_steps x {errors against the references -> u = u0 - K d, clipped as set_controls clips -> integrators (held per block
         while one of its controls is clipped) -> one RK4 of dt -> the references move at their own rates} in ONE launch (dt None:
         the fleet's own `dt` where it has one, else 0.01 s).  Needs design_servo() first.  `u` receives the last applied
         controls, `lqr_saturated_steps` [N] int32 counts the steps in which a control was clipped, `servo.err` holds the last
         errors.  The fleet integrates its airframes' own parameter blocks; where they differ from the designed ones the
-        integrators take up the difference.  wind: a servo.ServoWind, the air each aircraft flies in (None: still air)."""
+        integrators take up the difference.  wind: a servo.ServoWind, the air each aircraft flies in (None: still air).
+        schedule: a ServoSchedule (design_servo_schedule): the trim point and the gains of each control step are interpolated from
+        it at the measured airspeed (on="airspeed") or the commanded one (on="command"), and the design is not read: only the
+        loop's state (`servo`), which design_servo() starts, is needed.  Not together with wind (NotImplementedError)."""
         from . import servo as SV
-        design = self._need_servo("step_servo")
         if dt is None:
             dt = getattr(self, "dt", 0.01)
+        if schedule is not None:
+            self._need_servo_state("step_servo")
+            SV.step_into(self.precision, self.x, self._servo, self.servo, self.params, self.type_index, dt, n_steps, self.u,
+                         self._saturated_steps(), self.servo.err, wind=wind, schedule=schedule, on=on)
+            self.time += dt * n_steps
+            return
+        design = self._need_servo("step_servo")
         if wind is not None:
             SV.step_into(self.precision, self.x, design, self.servo, self.params, self.type_index, dt, n_steps, self.u,
                          self._saturated_steps(), self.servo.err, wind=wind)
@@ -182,17 +212,25 @@ class BatchedSixDOF:
         self.servo_mission = SV.ServoMission.start(waypoints, self.n, self.device, guidance_type, acceptance_radius, on_complete, flight_config)
         return self.servo_mission
 
-    def fly_servo_mission(self, n_steps: int = 1, dt: Optional[float] = None, wind=None):
+    def fly_servo_mission(self, n_steps: int = 1, dt: Optional[float] = None, wind=None, schedule=None, on: str = "airspeed"):
         """n_steps x {mission update -> guidance -> references -> the control step of step_servo} in ONE launch.  An aircraft whose
         mission is complete stops where it is.  `u`, `lqr_saturated_steps` and `servo.err` as step_servo leaves them; `time`
         advances by n_steps x dt (an aircraft's own flown time: servo_mission.mission_time(dt)).  wind: as step_servo takes it; the
-        guidance then reads the air-relative speed, course and position stay ground quantities (no wind-correction angle)."""
+        guidance then reads the air-relative speed, course and position stay ground quantities (no wind-correction angle).
+        schedule, on: as step_servo takes them; on="command" enters the table with the speed command the guidance has just written."""
         from . import servo as SV
-        design = self._need_servo("fly_servo_mission")
+        if schedule is not None:
+            self._need_servo_state("fly_servo_mission")
+        design = self._servo if schedule is not None else self._need_servo("fly_servo_mission")
         if self.servo_mission is None:
             raise ValueError(f"{type(self).__name__}.fly_servo_mission: the fleet has no mission; call .start_servo_mission() first")
         if dt is None:
             dt = getattr(self, "dt", 0.01)
+        if schedule is not None:
+            SV.mission_into(self.precision, self.x, design, self.servo, self.servo_mission, self.params, self.type_index, dt, n_steps, self.u,
+                            self._saturated_steps(), self.servo.err, wind=wind, schedule=schedule, on=on)
+            self.time += dt * n_steps
+            return
         if wind is not None:
             SV.mission_into(self.precision, self.x, design, self.servo, self.servo_mission, self.params, self.type_index, dt, n_steps, self.u,
                             self._saturated_steps(), self.servo.err, wind=wind)
@@ -208,6 +246,13 @@ class BatchedSixDOF:
         if self.servo_mission is None:
             raise ValueError(f"{type(self).__name__}.servo_mission_complete: the fleet has no mission; call .start_servo_mission() first")
         return self.servo_mission.complete()
+
+    def _need_servo_state(self, what: str):
+        """Under a schedule the single design is never read; what the flight needs is the loop's state (`servo`: references, integrators
+        and error clips), which design_servo() starts at the trim."""
+        if self.servo is None:
+            raise ValueError(f"{type(self).__name__}.{what}: the fleet has no servo state (references and integrators); "
+                             "call .design_servo() first, which starts it at the trim")
 
     def _need_servo(self, what: str):
         if self._servo is None:

@@ -303,10 +303,17 @@ class ServoWind:
 def step_into(precision: str, x: torch.Tensor, design: ServoDesign, state: ServoState, params: torch.Tensor,
               type_index: Optional[torch.Tensor], dt: float, n_steps: int, surf_out: Optional[torch.Tensor] = None,
               sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None, wind: Optional[ServoWind] = None,
-              z: Optional[torch.Tensor] = None):
+              z: Optional[torch.Tensor] = None, schedule=None, on: str = "airspeed"):
     """One launch of fdyn_servo_step_<precision>: x [12][n] in the precision's storage type, advanced in place with the state's
     references and integrators; n_steps = 0 writes surf_out alone.  With a `wind`, one launch of fdyn_servo_step_wind_<precision>
-    (its gust rows advanced, then its step counter by n_steps); z [n_steps][3][n] float64 replaces the in-kernel normals."""
+    (its gust rows advanced, then its step counter by n_steps); z [n_steps][3][n] float64 replaces the in-kernel normals.  With a
+    `schedule` (a servo_sched.ServoSchedule), one launch of fdyn_servo_sched_step_<precision>: the trim point and the gains are read
+    from the schedule, entered with the measured airspeed (on="airspeed") or the commanded one ("command"), and `design` is not."""
+    if schedule is not None:
+        if wind is not None or z is not None:
+            raise NotImplementedError("a gain schedule is flown in still air: schedule= and wind= exclude each other")
+        from . import servo_sched as SS
+        return SS.sched_step_into(precision, x, schedule, state, params, type_index, dt, n_steps, on, surf_out, sat_steps, err_out)
     if design.x0 is None or design.u0 is None:
         raise ValueError("the design carries no trim point (x0, u0)")
     n = int(x.shape[1])
@@ -380,10 +387,16 @@ class ServoMission:
 def mission_into(precision: str, x: torch.Tensor, design: ServoDesign, state: ServoState, mission: ServoMission, params: torch.Tensor,
                  type_index: Optional[torch.Tensor], dt: float, n_steps: int, surf_out: Optional[torch.Tensor] = None,
                  sat_steps: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None, wind: Optional[ServoWind] = None,
-                 z: Optional[torch.Tensor] = None):
+                 z: Optional[torch.Tensor] = None, schedule=None, on: str = "airspeed"):
     """One launch of fdyn_servo_mission_<precision>: n_steps x {mission update, guidance, servo law, RK4} on x [12][n], advanced in
     place with the state's references and integrators and the mission's words; n_steps = 0 writes surf_out alone.  With a `wind`,
-    one launch of fdyn_servo_mission_wind_<precision>, as step_into."""
+    one launch of fdyn_servo_mission_wind_<precision>, as step_into; with a `schedule`, one of fdyn_servo_sched_mission_<precision>,
+    as step_into."""
+    if schedule is not None:
+        if wind is not None or z is not None:
+            raise NotImplementedError("a gain schedule is flown in still air: schedule= and wind= exclude each other")
+        from . import servo_sched as SS
+        return SS.sched_mission_into(precision, x, schedule, state, mission, params, type_index, dt, n_steps, on, surf_out, sat_steps, err_out)
     if design.x0 is None or design.u0 is None:
         raise ValueError("the design carries no trim point (x0, u0)")
     n = int(x.shape[1])

@@ -336,6 +336,14 @@ enum { FD_SV_NOT_CONVERGED = 1, FD_SV_NO_CERTIFICATE = 2, FD_SV_BAD_INPUT = 4 };
  * the largest horizontal distance from the leg that ends at the active waypoint (m).  The host starts them at 0, 0, +inf, 0.
  * (FD_MST_*, not FD_MS_*: that prefix and FD_NMS belong to the sensor's measurement block below.)                          */
 enum { FD_MST_ALTITUDE_ERROR = 0, FD_MST_ROLL, FD_MST_MIN_AIRSPEED, FD_MST_CROSS_TRACK, FD_NMST = 4 };
+/* gain schedule sched [n_nodes][FD_NSS][n] fp64 of fdyn_servo_sched_* (include/fdyn_servo_sched.h), per node: its airspeed
+ * (m/s), the eight regulated trim words in the order the step kernel keeps them (u, w, q, theta, v, p, r, phi), the trim
+ * controls (FD_U_* order) and the gains as fdyn_servo_design writes them (FD_SVK_*).  1 <= n_nodes <= FD_MAX_SCHED_NODES.
+ * (FD_SS_*, FD_NSS, not FD_SC_*, FD_NSC: those belong to the per-aircraft scales above.)                                   */
+enum { FD_SS_V = 0, FD_SS_X0 = 1, FD_SS_U0 = 9, FD_SS_K = 13, FD_NSS = 39 };
+enum { FD_MAX_SCHED_NODES = 8 };
+/* sched_on: what the table is entered with, the airspeed as step 1 of the law forms it or the commanded airspeed          */
+enum { FD_SCHED_ON_AIRSPEED = 0, FD_SCHED_ON_COMMAND = 1 };
 
 /* ---- stand-alone reward evaluation (fdyn_rate_reward_seq_*), learned_controllers/envs/rewards.py ------------------- */
 /* parameters (fp64): RateTrackingReward weights :14-19, then SettlingTimeBonus :160-162                              */
