@@ -34,6 +34,10 @@
 //                     trim point and gains from LDS columns every step anyway; in front of each control step those columns are
 //                     rewritten from the two nodes of the aircraft's table that bracket its airspeed (or its speed command).
 //                     The table stays in global memory, [node][word][lane], so that a wave reads each word in one burst.
+// fdyn_servo_sched_lqg_step_*  the scheduled servo on noisy sensors (include/fdyn_servo_sched_lqg.h): the body a sixth time, with
+//                     an Estimator and a ScheduleLqg both on.  `reschedule` then interpolates the filter's 120 words as well and
+//                     moves the estimate and du_prev to the new operating point; everything it adds is behind the ScheduleLqg
+//                     argument type.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fdyn_fleet.hpp"
@@ -48,6 +52,7 @@
 #include "../../include/fdyn_servo_lqg.h"
 #include "../../include/fdyn_servo_lqg_mission.h"
 #include "../../include/fdyn_servo_sched.h"
+#include "../../include/fdyn_servo_sched_lqg.h"
 
 using namespace fdyn;
 
@@ -302,6 +307,9 @@ struct EstimatorPos : Estimator { const double* pos /*[2]*/; double* phat /*[2][
 // What fdyn_servo_sched_* add (include/fdyn_servo_sched.h); NoSchedule is the one design of x0, u0, K.
 struct NoSchedule {};
 struct Schedule { const double* table /*[n_nodes][FD_NSS][n]*/; int n_nodes; int on; double* sigma_out /*[2][n]*/; };
+// what fdyn_servo_sched_lqg_step_* add to the schedule (include/fdyn_servo_sched_lqg.h): the filters' table, the origin of the z and
+// psi words of the estimate, and the operating point the estimate is relative to
+struct ScheduleLqg : Schedule { const double* table_f /*[n_nodes][FD_NSKF][n]*/; const double* origin /*[2][n]*/; double* state /*[2][n]*/; };
 constexpr int DYN_F_BYTES = FD_NSKF * 64 * int(sizeof(double));
 // the ten estimated words inside x, their angles, and where the trim's word sits among the fp64 columns (z0, psi0 behind SD_LQG)
 __device__ constexpr int EST_W[FD_NSKX] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_D, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL, FD_X_YAW };
@@ -348,7 +356,9 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     constexpr bool LM = __is_same(EA, EstimatorPos);                             // the mission on the estimate
     static_assert(!LM || (MISSION && !WINDY), "the position filter belongs to the still-air mission");
     constexpr bool SCHED = !__is_same(SA, NoSchedule);
-    static_assert(!SCHED || (!WINDY && !LQG), "the schedule is flown in still air on the true state");
+    constexpr bool SL = __is_same(SA, ScheduleLqg);                              // the schedule on the estimate: the filter scheduled too
+    static_assert(!SCHED || (!WINDY && (!LQG || SL)), "the schedule is flown in still air; on noisy sensors only with a scheduled filter");
+    static_assert(!SL || (LQG && !LM && !MISSION && !__is_same(EA, EstimatorDynLds)), "the scheduled filter belongs to the control step");
     constexpr int NZ = LM ? FD_NSKZ : FD_NSKX;                                   // normals per step of a replayed z
     constexpr bool F_DYN = __is_same(EA, EstimatorDynLds);                       // fp64 glue: the filter's words in dynamic LDS
     constexpr bool F_LDS = LQG && sizeof(G) == 4;                                // the filter's words in LDS (fp32 glue) or read from F
@@ -357,8 +367,9 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     constexpr int SD_STAT = SD_N, SD_GUST = MISSION ? SD_N + FD_NMST : SD_N;      // WINDY: g [3], then A, B, then W [3]
     constexpr int SD_WIND = SD_GUST + 5, SD_LQG = WINDY ? SD_WIND + 3 : SD_GUST; // LQG: the trim's z and psi
     constexpr int SD_KEEP = SD_LQG + 2, SD_PHAT = SD_KEEP + FD_NSKX;             // and the true ten words while the law reads x_f; LM: phat [2]
-    constexpr int SD_SIG = SD_LQG, SD_POS = SD_SIG + 1;                          // SCHED: the sigma the law's columns hold, the position
-    constexpr int SD_WORDS = SCHED ? SD_POS + 1 : (LM ? SD_PHAT + 2 : (LQG ? SD_PHAT : SD_LQG));
+    constexpr int SD_SIG = SL ? SD_PHAT : SD_LQG, SD_POS = SD_SIG + 1;           // SCHED: the sigma the law's columns hold, the position
+    constexpr int SD_KN = SD_POS + 1, SD_T = SD_KN + 1;                          // SL: the lower node and t of the filter's words (t < 0: exact)
+    constexpr int SD_WORDS = SL ? SD_T + 1 : (SCHED ? SD_POS + 1 : (LM ? SD_PHAT + 2 : (LQG ? SD_PHAT : SD_LQG)));
     constexpr int SG_AIR = SG_N, SG_XHAT = WINDY ? SG_N + 3 : SG_N;              // WINDY: W + g [3]; LQG: xhat [10], du_prev [4], F [120]
     constexpr int SG_DU = SG_XHAT + FD_NSKX, SG_F = SG_DU + FD_NU;
     constexpr int SG_WORDS = LQG ? (F_LDS ? SG_F + FD_NSKF : SG_F) : SG_XHAT;
@@ -390,7 +401,10 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     }
     {
 #pragma clang fp contract(off)
-        if constexpr (SCHED) {
+        if constexpr (SL) {                                      // the operating point the caller's xhat and du_prev are relative to
+            ld.set(SD_SIG, sa.state[i]);
+            ld.set(SD_POS, sa.state[n + i]);
+        } else if constexpr (SCHED) {
             ld.set(SD_POS, -1.0);                                // no position is negative: the law's columns hold nothing yet
         } else {
             constexpr int W[8] = { FD_X_U, FD_X_W, FD_X_Q, FD_X_PITCH, FD_X_V, FD_X_P, FD_X_R, FD_X_ROLL };
@@ -421,8 +435,13 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             for (int k = 0; k < 3; ++k) ld.set(SD_WIND + k, wa.rows[int64_t(FD_SW_WIND_N + k) * n + i]);
         }
         if constexpr (LQG) {
-            ld.set(SD_LQG + 0, x0[FD_X_D * n + i]);
-            ld.set(SD_LQG + 1, x0[FD_X_YAW * n + i]);
+            if constexpr (SL) {
+                ld.set(SD_LQG + 0, sa.origin[i]);
+                ld.set(SD_LQG + 1, sa.origin[n + i]);
+            } else {
+                ld.set(SD_LQG + 0, x0[FD_X_D * n + i]);
+                ld.set(SD_LQG + 1, x0[FD_X_YAW * n + i]);
+            }
 #pragma unroll
             for (int j = 0; j < FD_NSKX; ++j) lg.set(SG_XHAT + j, G(ea.xhat[int64_t(j) * n + i]));
 #pragma unroll
@@ -431,7 +450,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
 #pragma unroll
                 for (int k = 0; k < 2; ++k) ld.set(SD_PHAT + k, ea.phat[int64_t(k) * n + i]);
             }
-            if constexpr (F_LDS) {                               // a few words at a time, before the physics' own registers are loaded
+            if constexpr (F_LDS && !SL) {                        // a few words at a time, before the physics' own registers are loaded
 #pragma unroll
                 for (int k = 0; k < FD_NSKF; ++k) {
                     if (k % 16 == 0) asm volatile("" ::: "memory");
@@ -513,14 +532,25 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     // SCHED, steps 0a-0c (include/fdyn_servo_sched.h): the law's columns from the two nodes that bracket sigma.  Skipped when sigma
     // is bitwise the one the columns were built from (on the command: nearly every step); the columns are then what this would
     // write.  Eight words in flight at a time, and everything it computes is dead when it returns.
-    auto reschedule = [&]() {
+    // SL (include/fdyn_servo_sched_lqg.h): the filter's words are interpolated with the others -- fp32 glue: into their columns;
+    // fp64 glue: the lower node and t are kept and `fword` interpolates from the table -- and the estimate and du_prev are moved to
+    // the new operating point.  `entry`: the call at launch entry, which rebuilds the columns from the stored sigma (or enters the
+    // table with V_c) and moves nothing.
+    auto reschedule = [&](bool entry = false) {
         if constexpr (SCHED) {
 #pragma clang fp contract(off)
             asm volatile("" ::: "memory");
             double sg;
-            if (sa.on == FD_SCHED_ON_COMMAND) sg = ld.get(SD_REF + FD_SVR_SPEED);
-            else sg = double(M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]));
-            if (ld.get(SD_POS) >= 0.0 && __double_as_longlong(sg) == __double_as_longlong(ld.get(SD_SIG))) return;
+            if constexpr (SL) {
+                if (entry) sg = ld.get(SD_POS) >= 0.0 ? ld.get(SD_SIG) : ld.get(SD_REF + FD_SVR_SPEED);
+                else if (sa.on == FD_SCHED_ON_COMMAND) sg = ld.get(SD_REF + FD_SVR_SPEED);
+                else sg = double(M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]));
+                if (!entry && __double_as_longlong(sg) == __double_as_longlong(ld.get(SD_SIG))) return;
+            } else {
+                if (sa.on == FD_SCHED_ON_COMMAND) sg = ld.get(SD_REF + FD_SVR_SPEED);
+                else sg = double(M<S>::sqrt((x[FD_X_U] * x[FD_X_U] + x[FD_X_V] * x[FD_X_V]) + x[FD_X_W] * x[FD_X_W]));
+                if (ld.get(SD_POS) >= 0.0 && __double_as_longlong(sg) == __double_as_longlong(ld.get(SD_SIG))) return;
+            }
             // the lane index and the row stride made opaque, as the estimator's: none of these addresses lives across the RK4
             int64_t il = i, nl = n;
             asm volatile("" : "+v"(il), "+s"(nl));
@@ -552,11 +582,46 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
                 const double a = lo[int64_t(r) * nl], b = hi[int64_t(r) * nl];
                 return exact ? a : a + t * (b - a);
             };
+            if constexpr (SL) {
+                // step 4: the estimate and du_prev to the new operating point, differences and sums in fp64
+                constexpr int XH[8] = { 0, 1, 2, 3, 5, 6, 7, 8 };  // (u, w, q, theta | v, p, r, phi) among the ten estimated words
 #pragma unroll
-            for (int r = 0; r < 8; ++r) ld.set(SD_X0 + r, word(FD_SS_X0 + r));
-            asm volatile("" ::: "memory");
+                for (int r = 0; r < 8; ++r) {
+                    const double was = ld.get(SD_X0 + r), now = word(FD_SS_X0 + r);
+                    ld.set(SD_X0 + r, now);
+                    if (!entry) {
+                        G xh = G(double(lg.get(SG_XHAT + XH[r])) + (was - now));
+                        if (est_angle(XH[r]) && !(xh >= G(-FD_PI) && xh < G(FD_PI))) xh = wrap_angle<G>(xh);
+                        lg.set(SG_XHAT + XH[r], xh);
+                    }
+                }
+                asm volatile("" ::: "memory");
 #pragma unroll
-            for (int r = 0; r < FD_NU; ++r) lg.set(SG_U0 + r, G(word(FD_SS_U0 + r)));
+                for (int r = 0; r < FD_NU; ++r) {
+                    const G was = lg.get(SG_U0 + r), now = G(word(FD_SS_U0 + r));
+                    lg.set(SG_U0 + r, now);
+                    if (!entry) lg.set(SG_DU + r, G(double(lg.get(SG_DU + r)) + (double(was) - double(now))));
+                }
+                if constexpr (F_LDS) {
+                    const double* __restrict__ flo = sa.table_f + il + int64_t(k * FD_NSKF) * nl;
+                    const double* __restrict__ fhi = exact ? flo : flo + int64_t(FD_NSKF) * nl;
+#pragma unroll
+                    for (int r = 0; r < FD_NSKF; ++r) {
+                        if (r % 8 == 0) asm volatile("" ::: "memory");
+                        const double a = flo[int64_t(r) * nl], b = fhi[int64_t(r) * nl];
+                        lg.set(SG_F + r, G(exact ? a : a + t * (b - a)));
+                    }
+                } else {
+                    ld.set(SD_KN, double(k));
+                    ld.set(SD_T, exact ? -1.0 : t);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) ld.set(SD_X0 + r, word(FD_SS_X0 + r));
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int r = 0; r < FD_NU; ++r) lg.set(SG_U0 + r, G(word(FD_SS_U0 + r)));
+            }
 #pragma unroll
             for (int r = 0; r < FD_NSVK; ++r) {
                 if (r % 8 == 4) asm volatile("" ::: "memory");
@@ -572,6 +637,7 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             ld.set(SD_POS, pos);
         }
     };
+    if constexpr (SL) reschedule(true);
 
     // one control step up to the integrators: returns the unclipped controls (Controls::set clips).  `advance` is false for the
     // controls-only call (n_steps = 0), which writes nothing.
@@ -652,8 +718,18 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
     if constexpr (LQG) lstep0 = ea.step ? uint32_t(*ea.step) : 0u;
     // the fp64 column of the trim's word j of the ten: SD_X0 holds (u, w, q, theta | v, p, r, phi), SD_LQG z and psi
     auto trim_word = [&](int j) -> double { return ld.get(j == 4 ? SD_LQG : (j == EST_PSI ? SD_LQG + 1 : (j < 4 ? SD_X0 + j : SD_X0 + j - 1))); };
+    // SL, fp64 glue: the two nodes' rows of the filter at this lane and t, set at the top of `estimate` and dead when it returns
+    const double* __restrict__ f_lo = nullptr;
+    const double* __restrict__ f_hi = nullptr;
+    double f_t = 0.0;
+    bool f_exact = true;
     auto fword = [&](int k) -> G {
         if constexpr (F_LDS) return lg.get(SG_F + k);
+        else if constexpr (SL) {
+#pragma clang fp contract(off)
+            const double a = f_lo[int64_t(k) * nl], b = f_hi[int64_t(k) * nl];
+            return G(f_exact ? a : a + f_t * (b - a));
+        }
         else if constexpr (F_DYN) { extern __shared__ double s_dyn_f[]; return G(s_dyn_f[k * LB + threadIdx.x]); }
         else if constexpr (LQG) return G(ea.F[int64_t(k) * nl + il]);
         else return G(0);
@@ -690,6 +766,13 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             // register at the join: start again from the arguments instead
             if constexpr (LM) { il = i; nl = n; }
             asm volatile("" : "+v"(il), "+s"(nl) :: "memory");   // the filter words are re-read every step, as the law's
+            if constexpr (SL && !F_LDS) {
+                const double tt = ld.get(SD_T);
+                f_exact = tt < 0.0;
+                f_t = f_exact ? 0.0 : tt;
+                f_lo = sa.table_f + il + int64_t(int(ld.get(SD_KN)) * FD_NSKF) * nl;
+                f_hi = f_exact ? f_lo : f_lo + int64_t(FD_NSKF) * nl;
+            }
             float zn[12] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
             if (!ea.z) servo_lqg_normals(ea.seed, i, lstep0 + uint32_t(s) + 1u, zn);
             if constexpr (LM) { zpos[0] = zn[FD_NSKX]; zpos[1] = zn[FD_NSKX + 1]; }
@@ -1050,7 +1133,9 @@ FD_DEV void servo_step_body(S* __restrict__ xs /*[12][n]*/, const double* __rest
             for (int k = 0; k < FD_NU; ++k) ea.du_prev[int64_t(k) * n + ie] = double(lg.get(SG_DU + k));
         }
     }
-    if constexpr (SCHED) {
+    if constexpr (SL) {
+        if (n_steps > 0) { sa.state[ie] = ld.get(SD_SIG); sa.state[n + ie] = ld.get(SD_POS); }
+    } else if constexpr (SCHED) {
         if (sa.sigma_out) { sa.sigma_out[ie] = ld.get(SD_SIG); sa.sigma_out[n + ie] = ld.get(SD_POS); }
     }
     if (surf_out) {                                              // the controls as applied: after set_controls' clip
@@ -1140,6 +1225,34 @@ servo_sched_mission_kernel(S* __restrict__ xs, double* __restrict__ ref, double*
 {
     servo_step_body<S, T, true>(xs, nullptr, nullptr, nullptr, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps,
                                 err_out, m, NoWind{}, NoEstimator{}, sc);
+}
+
+template <typename S, typename T>
+__global__ void __launch_bounds__(LB, 1)
+servo_sched_lqg_step_kernel(S* __restrict__ xs, double* __restrict__ ref, double* __restrict__ integ, const double* __restrict__ limits,
+                            const uint8_t* __restrict__ type, const double* __restrict__ params, int n_types, int64_t n, S dt, int n_steps,
+                            S* __restrict__ surf_out, int32_t* __restrict__ sat_steps, double* __restrict__ err_out, Estimator e, ScheduleLqg sc)
+{
+    servo_step_body<S, T, false>(xs, nullptr, nullptr, nullptr, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps,
+                                 err_out, NoMission{}, NoWind{}, e, sc);
+}
+
+// refusals in launch_sched's order, then launch_lqg_step's
+template <typename S, typename T>
+int launch_sched_lqg(S* x, const ScheduleLqg& sc, double* ref, double* integ, const double* limits, const uint8_t* type, const double* params,
+                     int n_types, int64_t n, double dt, int n_steps, S* surf_out, int32_t* sat_steps, double* err_out, const Estimator& e,
+                     void* stream)
+{
+    if (n_steps < 0) return FDYN_ERR_BAD_SIZE;
+    if (sc.n_nodes < 1 || sc.n_nodes > FD_MAX_SCHED_NODES) return FDYN_ERR_BAD_SIZE;
+    if (sc.on != FD_SCHED_ON_AIRSPEED && sc.on != FD_SCHED_ON_COMMAND) return FDYN_ERR_BAD_SIZE;
+    FD_CHECK_FLEET(n, n_types, LB)
+    if (!x || !sc.table || !sc.table_f || !sc.origin || !ref || !integ || !limits || !params) return FDYN_ERR_NULL;
+    if (!e.sigma || !e.xhat || !e.du_prev || !sc.state) return FDYN_ERR_NULL;
+    if (e.feedback != FD_LQG_ESTIMATE && e.feedback != FD_LQG_MEASUREMENT && e.feedback != FD_LQG_TRUTH) return FDYN_ERR_BAD_SIZE;
+    if (bad_dt(dt)) return FDYN_ERR_BAD_DT;
+    return launch<LB>(servo_sched_lqg_step_kernel<S, T>, n, stream, x, ref, integ, limits, type, params, n_types, n, S(dt), n_steps, surf_out,
+                      sat_steps, err_out, e, sc);
 }
 
 // `m`: NULL for fdyn_servo_sched_step_*.  Refusals in launch_step's / launch_mission's order, the schedule's own with the sizes
@@ -1374,5 +1487,25 @@ FD_SERVO_SCHED(f64, double, double)
 FD_SERVO_SCHED(mixed, double, float)
 FD_SERVO_SCHED(f32, float, float)
 #undef FD_SERVO_SCHED
+
+#define FD_SERVO_SCHED_LQG(NAME, S, T)                                                                                                 \
+    int fdyn_servo_sched_lqg_step_##NAME(S* x, const double* sched, const double* sched_f, int n_nodes, int sched_on, const double* origin, \
+                                         double* ref, double* integ, const double* limits, const uint8_t* type, const double* params, \
+                                         int n_types, int64_t n, double dt, int n_steps, S* surf_out, int32_t* sat_steps,             \
+                                         double* err_out, const double* sigma, double* xhat, double* du_prev, double* sched_state,    \
+                                         uint64_t seed, const int32_t* step, const double* z, int feedback, double* err_est,          \
+                                         double* err_meas, double* chatter, double* meas_out, void* stream)                           \
+    {                                                                                                                                  \
+        ScheduleLqg sc;                                                                                                                \
+        static_cast<Schedule&>(sc) = Schedule{ sched, n_nodes, sched_on, nullptr };                                                    \
+        sc.table_f = sched_f; sc.origin = origin; sc.state = sched_state;                                                              \
+        const Estimator e{ nullptr, sigma, xhat, du_prev, seed, step, z, feedback, err_est, err_meas, chatter, meas_out };             \
+        return launch_sched_lqg<S, T>(x, sc, ref, integ, limits, type, params, n_types, n, dt, n_steps, surf_out, sat_steps, err_out,  \
+                                      e, stream);                                                                                      \
+    }
+FD_SERVO_SCHED_LQG(f64, double, double)
+FD_SERVO_SCHED_LQG(mixed, double, float)
+FD_SERVO_SCHED_LQG(f32, float, float)
+#undef FD_SERVO_SCHED_LQG
 
 }  // extern "C"

@@ -24,6 +24,7 @@ class BatchedSixDOF:
     servo_mission = None         # the last start_servo_mission()
     _servo_kalman = servo_lqg = None    # the last design_servo_kalman() and the ServoLqgState it started
     servo_position = servo_position_state = None    # the last start_servo_lqg_mission(): ServoPositionFilter, ServoLqgMissionState
+    _servo_kalman_schedule = servo_sched_lqg = None # the last design_servo_kalman_schedule() and the ServoSchedLqgState it started
 
     def __init__(self, n: int, precision: str = "f64", types: Sequence = ("rc_plane",),
                  type_index: Optional[np.ndarray] = None, device=None):
@@ -275,14 +276,47 @@ class BatchedSixDOF:
         self.servo_lqg = SL.ServoLqgState.zeros(self.n, self.device, seed=getattr(self, "seed", 0) or 0)
         return out
 
-    def step_servo_lqg(self, n_steps: int = 1, feedback: str = "estimate", z=None):
+    def design_servo_kalman_schedule(self, schedule, dt: float, noise=None, strict: bool = True):
+        """A Kalman filter for every node of a ServoSchedule (design_servo_schedule), each on its own trim's model discretised at
+        `dt` (hcrl_amd.servo_sched_lqg): ServoKalmanSchedule with table_f [M][120][N], for `step_servo_lqg(schedule=...)`.  noise as
+        design_servo_kalman takes it.  One linearise and one design launch over M N lanes.  strict: ValueError when a node has no
+        certified filter.  Also starts the scheduled estimator's state (`servo_sched_lqg`: estimate zero, no operating point yet,
+        step word 0).  The fleet's state, trim, design and single filter are not touched."""
+        from . import servo_sched_lqg as SQ
+        out = SQ.design_servo_kalman_schedule(schedule, dt, noise, strict=False)
+        if strict:
+            out.require_ok(f"{type(self).__name__}.design_servo_kalman_schedule")
+        self._servo_kalman_schedule = out
+        self.servo_sched_lqg = SQ.ServoSchedLqgState.zeros(self.n, self.device, seed=getattr(self, "seed", 0) or 0)
+        return out
+
+    def step_servo_lqg(self, n_steps: int = 1, feedback: str = "estimate", z=None, schedule=None, on: str = "airspeed"):
         """n_steps x {measure the ten words with the sensor noise -> Kalman update, heading innovation wrapped -> the control step
         of step_servo on trim + f -> one RK4 of the filter's dt -> the references move} in ONE launch, f = the estimate, the raw
         measurement or the true state.  Needs design_servo() and design_servo_kalman() first.  z: None = in-kernel Philox draws
         keyed by `servo_lqg.seed` and `servo_lqg.step`, or [n_steps][10][N] float64 standard normals.  `u`, `lqr_saturated_steps`
         and `servo.err` (the errors of the TRUE state) as step_servo leaves them; `servo_lqg` carries the estimate and the
-        accumulators (err_est, err_meas, chatter)."""
+        accumulators (err_est, err_meas, chatter).
+        schedule: a ServoSchedule whose filters design_servo_kalman_schedule() has made: the trim point, the gains and the filter of
+        each control step are interpolated from the two tables at the airspeed of the law's input (on="airspeed") or at the commanded
+        one (on="command"), the estimate is relative to the operating point and moves with it, and neither the single design nor
+        the single filter is read: the loop's state (`servo`), the fleet's trim (the origin of the altitude and heading words) and
+        `servo_sched_lqg` are.  A schedule without a filter schedule is a ValueError, and so is one whose filters were made at
+        another dt than the fleet's single filter."""
         from . import servo_lqg as SL
+        if schedule is not None:
+            from . import servo_sched_lqg as SQ
+            self._need_servo_state("step_servo_lqg")
+            res, _ = self._need_trim("step_servo_lqg")
+            kalman = self._servo_kalman_schedule
+            if kalman is None or kalman.schedule is not schedule:
+                raise ValueError(f"{type(self).__name__}.step_servo_lqg: the schedule has no filter schedule; call "
+                                 ".design_servo_kalman_schedule(schedule, dt) first")
+            dt = kalman.dt if self._servo_kalman is None else self._servo_kalman.dt
+            SQ.sched_lqg_step_into(self.precision, self.x, schedule, kalman, SQ.origin_of(res.x0), self.servo, self.servo_sched_lqg, self.params,
+                                   self.type_index, dt, n_steps, feedback, on, z, self.u, self._saturated_steps(), self.servo.err)
+            self.time += dt * n_steps
+            return
         design = self._need_servo("step_servo_lqg")
         if self._servo_kalman is None:
             raise ValueError(f"{type(self).__name__}.step_servo_lqg: the fleet has no servo filter; call .design_servo_kalman() first")
