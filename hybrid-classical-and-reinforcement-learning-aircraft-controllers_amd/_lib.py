@@ -79,6 +79,9 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_sched.h"))
 # and the scheduled servo on noisy sensors, its filter scheduled too (include/fdyn_servo_sched_lqg.h): a twelfth
 with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_sched_lqg.h")) as _f:
     SERVO_SCHED_LQG_SIGNATURES = _parse_header(_f.read(), "include/fdyn_servo_sched_lqg.h")[0]
+# and the servo's sampled-data design (include/fdyn_servo_dt.h): a thirteenth
+with open(os.path.join(os.path.dirname(_HERE), "include", "fdyn_servo_dt.h")) as _f:
+    SERVO_DT_SIGNATURES = _parse_header(_f.read(), "include/fdyn_servo_dt.h")[0]
 
 _lib = None
 
@@ -106,7 +109,7 @@ def load():
                                   *WIND_SIGNATURES.items(), *SERVO_LQG_SIGNATURES.items(), *SERVO_MARGIN_SIGNATURES.items(),
                                   *SERVO_MODES_SIGNATURES.items(), *SERVO_LQG_MISSION_SIGNATURES.items(),
                                   *SERVO_COVARIANCE_SIGNATURES.items(), *SERVO_SCHED_SIGNATURES.items(),
-                                  *SERVO_SCHED_LQG_SIGNATURES.items()):
+                                  *SERVO_SCHED_LQG_SIGNATURES.items(), *SERVO_DT_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = header/library drift
             fn.restype, fn.argtypes = res, args
         if lib.fdyn_abi_version() != FDYN_ABI_VERSION:

@@ -132,15 +132,18 @@ class BatchedSixDOF:
         self.time += dt * n_steps
 
     # LQ servo (hcrl_amd.servo): LQR with integral action, flown to heading, speed and altitude commands
-    def design_servo(self, weights=None, scales=None, strict: bool = True):
+    def design_servo(self, weights=None, scales=None, strict: bool = True, dt: Optional[float] = None):
         """An LQ-servo gain for every aircraft at the fleet's current trim (the last `.trim(...)`): ServoDesign with K [26][N],
         status 0 = a certified stabilising gain.  weights: None (ServoWeights()), a ServoWeights, or penalties [17] / [17][N];
         scales: None = the multipliers the trim was solved with.  strict: raise ValueError when an aircraft has no certified
         gain.  Also starts the loop's state (`servo`: references at the trim's own airspeed, altitude and heading, moving at its
-        climb rate and turn rate; integrators zero).  The fleet's state is not touched."""
+        climb rate and turn rate; integrators zero).  The fleet's state is not touched.
+        dt: None = the continuous design, flown at any step; a control step = the sampled-data design for the loop as step_servo
+        flies it at that step (hold and Euler integrators in the model).  It is then flown and analysed at that step only: another
+        is a ValueError."""
         from . import servo as SV
         res, trim_scales = self._need_trim("design_servo")
-        out = SV.design_servo(res, self.params, self.type_index, trim_scales if scales is None else scales, weights)
+        out = SV.design_servo(res, self.params, self.type_index, trim_scales if scales is None else scales, weights, dt)
         if strict:
             SV.require_ok(out, f"{type(self).__name__}.design_servo")
         self._servo = out
@@ -154,14 +157,15 @@ class BatchedSixDOF:
         self.servo.command(heading, speed, altitude)
 
     def design_servo_schedule(self, airspeeds, climb=0.0, turn=0.0, altitude=None, heading=None, weights=None, scales=None,
-                              strict: bool = True):
+                              strict: bool = True, dt: Optional[float] = None):
         """A table of LQ-servo designs over airspeed for every aircraft (hcrl_amd.servo_sched): ServoSchedule with table
         [M][FD_NSS][N], for `step_servo(schedule=...)` and `fly_servo_mission(schedule=...)`.  airspeeds: M <= FD_MAX_SCHED_NODES
         strictly increasing values, or [M][N]; climb (rad), turn (rad/s), altitude and heading: the other words of the nodes' flight
         condition (altitude, heading None: those of the fleet's current trim, else 100 m and 0); weights and scales as design_servo
         takes them (scales None: the multipliers of the current trim, if any).  One trim, one linearise and one design launch over
         M N lanes.  ValueError for airspeeds that are not strictly increasing or for too many nodes; strict: also when a node has no
-        trim or no certified gain.  The fleet's state, trim and design are not touched."""
+        trim or no certified gain.  The fleet's state, trim and design are not touched.  dt: as design_servo takes it; every node
+        is then the sampled-data design for that control step, and the schedule is flown at that step only."""
         from . import servo_sched as SS
         trim_scales = None
         if self._trim is not None:
@@ -169,7 +173,8 @@ class BatchedSixDOF:
             altitude = -res.x0[L.FD_X_D] if altitude is None else altitude
             heading = res.x0[L.FD_X_YAW] if heading is None else heading
         out = SS.design_servo_schedule(airspeeds, self.n, self.params, self.type_index, climb, turn, 100.0 if altitude is None else altitude,
-                                       0.0 if heading is None else heading, weights, trim_scales if scales is None else scales, strict=False)
+                                       0.0 if heading is None else heading, weights, trim_scales if scales is None else scales, strict=False,
+                                       dt=dt)
         if strict:
             out.require_ok(f"{type(self).__name__}.design_servo_schedule")
         return out

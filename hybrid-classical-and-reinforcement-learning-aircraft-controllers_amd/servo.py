@@ -24,6 +24,12 @@ Both fly in a moving air mass when given a `ServoWind` (include/fdyn_wind.h: a s
     fleet.x.copy_(wind.ground_state(fleet.x))         # a still-air trim, put in trim relative to its air
     fleet.fly_servo_mission(n_steps=6000, dt=0.01, wind=wind)
 
+A fleet flown at one fixed control step can have its gain designed for that step (`fdyn_servo_design_dt`, include/fdyn_servo_dt.h:
+the zero-order hold and the forward-Euler integrators in the model, the discrete Riccati equation); the design then carries its `dt`
+and is flown and analysed at that step only:
+
+    fleet.design_servo(dt=0.02)                   # ServoDesign.dt == 0.02; step_servo(n, 0.01) is a ValueError
+
 Nothing here synchronises with the device except `describe_status` on a tensor element, `count_not_ok` and the `strict` check,
 which read results back on purpose.
 """
@@ -104,6 +110,7 @@ class ServoDesign(T.StatusResult):
     status: torch.Tensor                    # [n] int32: FD_SV_* bits, 0 = a certified stabilising gain
     x0: Optional[torch.Tensor] = None       # [12][n] float64: the trim the model was cut at
     u0: Optional[torch.Tensor] = None       # [4][n]  float64
+    dt: Optional[float] = None              # the control step a sampled-data design was made for (None: the continuous design)
 
     def gains(self):
         """(K_lon [2][7][n], K_lat [2][6][n]): views of K."""
@@ -164,11 +171,41 @@ def servo_into(A: torch.Tensor, B: torch.Tensor, x0: torch.Tensor, weights: torc
     return out
 
 
-def design_servo(trim_result, params: torch.Tensor, type_index=None, scales=None, weights=None) -> ServoDesign:
+def servo_dt_into(A: torch.Tensor, B: torch.Tensor, x0: torch.Tensor, weights: torch.Tensor, dt: float,
+                  out: Optional[ServoDesign] = None) -> ServoDesign:
+    """One launch of fdyn_servo_design_dt (include/fdyn_servo_dt.h) on the tensors `servo_into` takes: the gain designed for the
+    loop as `step_into` flies it at the control step dt -- the discrete Riccati equation of the plant behind a zero-order hold
+    with forward-Euler integrators.  The ServoDesign carries that `dt`; flying or analysing it at another step is a ValueError."""
+    n, dev = T.check_model(A, B, weights, "weights", L.FD_NSVW), A.device
+    if tuple(x0.shape) != (L.FD_NX, n) or x0.dtype != torch.float64:
+        raise ValueError(f"x0 must be [12][{n}] float64, got {tuple(x0.shape)} {x0.dtype}")
+    if out is None:
+        out = ServoDesign(torch.empty((L.FD_NSVK, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                          torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    rc = _lib.load().fdyn_servo_design_dt(_lib.ptr(A), _lib.ptr(B), _lib.ptr(x0), _lib.ptr(weights), int(weights.dim() == 2), float(dt), n,
+                                          _lib.ptr(out.K), _lib.ptr(out.residual), _lib.ptr(out.iterations), _lib.ptr(out.status),
+                                          _lib.current_stream())
+    _lib.check(rc, "fdyn_servo_design_dt")
+    out.dt = float(dt)
+    return out
+
+
+def check_step(designed, dt, what: str):
+    """ValueError when a gain designed for one control step (a ServoDesign or a ServoSchedule whose `dt` is set) is to be flown or
+    analysed at another.  A continuous design (dt None) passes at any step."""
+    made = getattr(designed, "dt", None)
+    if made is not None and abs(float(made) - float(dt)) > 1e-12 * max(abs(float(made)), abs(float(dt))):
+        raise ValueError(f"{what}: the servo gain was designed for a control step of {float(made):g} s and cannot run at {float(dt):g} s; "
+                         f"design it again with dt={float(dt):g}")
+
+
+def design_servo(trim_result, params: torch.Tensor, type_index=None, scales=None, weights=None, dt: Optional[float] = None) -> ServoDesign:
     """Linearise every aircraft at its trim (fdyn_linearize at x0, u0), then design.  params [n_types][FD_NP] on the device;
-    type_index [n] or None; scales as `trim.scale_rows` takes them; weights as `weights_tensor` takes them."""
+    type_index [n] or None; scales as `trim.scale_rows` takes them; weights as `weights_tensor` takes them.  dt: None = the
+    continuous design (fdyn_servo_design); a control step = the sampled-data design for that step (fdyn_servo_design_dt)."""
     A, B = T.linearize_at_trim(trim_result, params, type_index, scales)
-    out = servo_into(A, B, trim_result.x0, weights_tensor(weights, trim_result.n, A.device))
+    w = weights_tensor(weights, trim_result.n, A.device)
+    out = servo_into(A, B, trim_result.x0, w) if dt is None else servo_dt_into(A, B, trim_result.x0, w, dt)
     out.x0, out.u0 = trim_result.x0, trim_result.u0
     return out
 
@@ -316,6 +353,7 @@ def step_into(precision: str, x: torch.Tensor, design: ServoDesign, state: Servo
         return SS.sched_step_into(precision, x, schedule, state, params, type_index, dt, n_steps, on, surf_out, sat_steps, err_out)
     if design.x0 is None or design.u0 is None:
         raise ValueError("the design carries no trim point (x0, u0)")
+    check_step(design, dt, "step_into")
     n = int(x.shape[1])
     if x.dtype != _lib.state_dtype(precision) or design.n != n or state.n != n:
         raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and the servo state of that fleet")
@@ -399,6 +437,7 @@ def mission_into(precision: str, x: torch.Tensor, design: ServoDesign, state: Se
         return SS.sched_mission_into(precision, x, schedule, state, mission, params, type_index, dt, n_steps, on, surf_out, sat_steps, err_out)
     if design.x0 is None or design.u0 is None:
         raise ValueError("the design carries no trim point (x0, u0)")
+    check_step(design, dt, "mission_into")
     n = int(x.shape[1])
     if x.dtype != _lib.state_dtype(precision) or design.n != n or state.n != n or mission.n != n:
         raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and the servo state and the mission of that fleet")

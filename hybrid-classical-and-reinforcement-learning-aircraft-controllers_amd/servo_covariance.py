@@ -194,6 +194,8 @@ def servo_covariance(servo_design, kalman_design, x0: Optional[torch.Tensor] = N
         raise ValueError("servo_covariance: the servo design carries no trim; give x0 [12][n]")
     if dt is not None and float(dt) != float(kalman_design.dt):
         raise ValueError(f"servo_covariance: the filter was designed at dt {kalman_design.dt}, got dt {dt}")
+    from .servo import check_step
+    check_step(servo_design, kalman_design.dt, "servo_covariance")
     if sigma is None:
         sigma = getattr(kalman_design, "sigma", None)
     if sigma is None:

@@ -191,6 +191,7 @@ def lqg_step_into(precision: str, x: torch.Tensor, design: SV.ServoDesign, kalma
         raise ValueError("the servo design carries no trim point (x0, u0)")
     if kalman.sigma is None:
         raise ValueError("the Kalman design carries no measurement noise (sigma)")
+    SV.check_step(design, dt, "lqg_step_into")
     n = int(x.shape[1])
     if x.dtype != _lib.state_dtype(precision) or design.n != n or kalman.n != n or state.n != n or int(lqg_state.xhat.shape[1]) != n:
         raise ValueError(f"x must be [12][{design.n}] {_lib.state_dtype(precision)}, and both designs and both states of that fleet")

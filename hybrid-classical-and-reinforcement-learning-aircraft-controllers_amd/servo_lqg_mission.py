@@ -111,6 +111,7 @@ def lqg_mission_into(precision: str, x: torch.Tensor, design: SV.ServoDesign, ka
         raise ValueError("the servo design carries no trim point (x0, u0)")
     if kalman.sigma is None:
         raise ValueError("the Kalman design carries no measurement noise (sigma)")
+    SV.check_step(design, dt, "lqg_mission_into")
     n = int(x.shape[1])
     if (x.dtype != _lib.state_dtype(precision) or design.n != n or kalman.n != n or state.n != n or mission.n != n
             or int(lqg_state.xhat.shape[1]) != n or int(pos_state.phat.shape[1]) != n):

@@ -23,6 +23,7 @@ import torch
 from . import _lib, layout as L
 from .lqg import FEEDBACK
 from .margins import MAX_OMEGA, LoopMargins, default_grid, unit_circle
+from .servo import check_step
 
 
 def servo_margins_into(K: torch.Tensor, F: torch.Tensor, x0: torch.Tensor, dt: float, zre: torch.Tensor, zim: torch.Tensor,
@@ -83,6 +84,7 @@ def servo_loop_margins(servo_design, servo_kalman_design, x0: Optional[torch.Ten
     if x0 is None:
         raise ValueError("servo_loop_margins: the servo design carries no trim; give x0 [12][n]")
     dt = float(servo_kalman_design.dt)
+    check_step(servo_design, dt, "servo_loop_margins")
     w = default_grid(dt) if omega is None else np.asarray(omega.detach().cpu() if isinstance(omega, torch.Tensor) else omega, np.float64)
     zre, zim = unit_circle(w, dt)
     dev = servo_design.K.device

@@ -206,4 +206,6 @@ def sampled_poles(design, kalman, x0: Optional[torch.Tensor] = None, out: Option
     x0 = design.x0 if x0 is None else x0
     if x0 is None:
         raise ValueError("sampled_poles: the servo design carries no trim; give x0 [12][n]")
+    from .servo import check_step
+    check_step(design, kalman.dt, "sampled_poles")
     return sampled_modes_into(design.K, kalman.F, x0, float(kalman.dt), out)

@@ -11,6 +11,7 @@ are one trim, one linearise and one `fdyn_servo_design` launch over M x n lanes.
     fleet.command_servo(speed=30.0)
     fleet.step_servo(n_steps=100, dt=0.01, schedule=sched)          # on="airspeed" | "command"
     sched.frozen_point_modes()                                      # the poles of A - B K between the nodes
+    fleet.design_servo_schedule((15.0, 20.0, 25.0, 30.0), dt=0.02)  # every node the sampled-data design for that step (servo.servo_dt_into)
 
 Still air and the true state only.  The flight entry points (`sched_step_into`, `sched_mission_into`) never synchronise with the
 device.  The design does, before anything is launched: `strict` reads the status back, and node airspeeds or flight-condition
@@ -74,6 +75,7 @@ class ServoSchedule:
     status: torch.Tensor                    # [M][n] int32: FD_SV_* bits of each node's design (FD_SV_BAD_INPUT also: no trim there)
     x0: Optional[torch.Tensor] = None       # [12][M n] float64: the nodes' trims, lane k n + i = node k of aircraft i
     context: Optional[dict] = None          # what frozen_point_modes trims and linearises with
+    dt: Optional[float] = None              # the control step sampled-data nodes were designed for (None: continuous designs)
 
     @property
     def n(self) -> int:
@@ -106,7 +108,7 @@ class ServoSchedule:
             raise ValueError("the design carries no trim point (x0, u0)")
         u, w = design.x0[L.FD_X_U], design.x0[L.FD_X_W]
         V = torch.sqrt(u * u + w * w)[None]
-        return cls(pack(V, design.x0, design.u0, design.K), V, design.status[None].clone(), design.x0)
+        return cls(pack(V, design.x0, design.u0, design.K), V, design.status[None].clone(), design.x0, dt=design.dt)
 
     def interpolated(self, position: torch.Tensor) -> torch.Tensor:
         """[FD_NSS][n]: the words at the table positions k + t [n] (0 <= position <= M - 1), as step 0b forms them, with torch ops."""
@@ -142,8 +144,9 @@ class ServoSchedule:
 
 
 def design_servo_schedule(airspeeds, n: int, params: torch.Tensor, type_index=None, climb=0.0, turn=0.0, altitude=100.0, heading=0.0,
-                          weights=None, scales=None, strict: bool = True) -> ServoSchedule:
-    """Trim, linearise and design n aircraft at M airspeeds each: one launch of fdyn_trim, fdyn_linearize and fdyn_servo_design over
+                          weights=None, scales=None, strict: bool = True, dt: Optional[float] = None) -> ServoSchedule:
+    """Trim, linearise and design n aircraft at M airspeeds each: one launch of fdyn_trim, fdyn_linearize and fdyn_servo_design (dt
+    None) or fdyn_servo_design_dt (the sampled-data design for the control step dt; the schedule then carries that `dt`) over
     M n lanes, then a torch pack.  airspeeds: M values for the whole fleet, or [M][n]; the other flight-condition words, weights
     and scales as trim_fleet and design_servo take them (per aircraft: shared by its nodes).  ValueError for airspeeds that are not
     strictly increasing or for M > FD_MAX_SCHED_NODES; strict: ValueError when a node has no trim or no certified gain."""
@@ -160,11 +163,12 @@ def design_servo_schedule(airspeeds, n: int, params: torch.Tensor, type_index=No
     tr = T.trim_into(spec_d, params, tile(tidx), tile(sc))
     A, B = T.linearize_into(tr.x0, tr.u0, params, tile(tidx), tile(sc))
     w = SV.weights_tensor(weights, n, dev)
-    d = SV.servo_into(A, B, tr.x0, tile(w) if w.dim() == 2 else w)
+    w = tile(w) if w.dim() == 2 else w
+    d = SV.servo_into(A, B, tr.x0, w) if dt is None else SV.servo_dt_into(A, B, tr.x0, w, dt)
     status = (d.status | (tr.status != 0).to(torch.int32) * L.FD_SV_BAD_INPUT).reshape(M, n)
     V_d = torch.as_tensor(V, device=dev)
     out = ServoSchedule(pack(V_d, tr.x0, tr.u0, d.K), V_d, status, tr.x0,
-                        dict(spec=torch.as_tensor(rows, device=dev), params=params, type_index=tidx, scales=sc))
+                        dict(spec=torch.as_tensor(rows, device=dev), params=params, type_index=tidx, scales=sc), d.dt)
     if strict:
         out.require_ok()
     return out
@@ -176,6 +180,7 @@ def sched_step_into(precision: str, x: torch.Tensor, schedule: ServoSchedule, st
     """One launch of fdyn_servo_sched_step_<precision>: step_into with the design read from the schedule; sigma_out [2][n] float64
     receives sigma and the table position of the last control step.  n_steps = 0 writes surf_out and sigma_out alone."""
     n = _check(precision, x, schedule, state, sigma_out)
+    SV.check_step(schedule, dt, "sched_step_into")
     rc = getattr(_lib.load(), f"fdyn_servo_sched_step_{precision}")(
         _lib.ptr(x), _lib.ptr(schedule.table), schedule.n_nodes, sched_on(on), _lib.ptr(state.ref), _lib.ptr(state.integ), _lib.ptr(state.limits),
         _lib.ptr(type_index), _lib.ptr(params), int(params.shape[0]), n, float(dt), int(n_steps), _lib.ptr(surf_out), _lib.ptr(sat_steps),
@@ -189,6 +194,7 @@ def sched_mission_into(precision: str, x: torch.Tensor, schedule: ServoSchedule,
                        sigma_out: Optional[torch.Tensor] = None):
     """One launch of fdyn_servo_sched_mission_<precision>: mission_into with the design read from the schedule."""
     n = _check(precision, x, schedule, state, sigma_out)
+    SV.check_step(schedule, dt, "sched_mission_into")
     if mission.n != n:
         raise ValueError(f"the mission holds {mission.n} aircraft, the fleet {n}")
     rc = getattr(_lib.load(), f"fdyn_servo_sched_mission_{precision}")(

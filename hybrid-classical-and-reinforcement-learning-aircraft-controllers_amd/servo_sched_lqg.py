@@ -173,6 +173,7 @@ def sched_lqg_step_into(precision: str, x: torch.Tensor, schedule: SS.ServoSched
         raise ValueError(f"the filter schedule was designed at dt = {kalman.dt}, the flight asks for dt = {float(dt)}")
     if kalman.sigma is None:
         raise ValueError("the filter schedule carries no measurement noise (sigma)")
+    SV.check_step(schedule, dt, "sched_lqg_step_into")
     n = SS._check(precision, x, schedule, state, None)
     if (kalman.n_nodes, kalman.n) != (schedule.n_nodes, n) or tuple(kalman.table_f.shape[1:]) != (L.FD_NSKF, n) or kalman.table_f.dtype != torch.float64:
         raise ValueError(f"the filter schedule must be [{schedule.n_nodes}][{L.FD_NSKF}][{n}] float64 beside the schedule's table, got "
